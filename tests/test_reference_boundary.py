@@ -6,7 +6,11 @@ the reference's shipped JSON config, and the REFERENCE's ``HRNetManager.forward_
 drives them.
 
 Runs in this build container only (the reference checkout is not on the GPU box) and in a subprocess (the import
-shim patches ``torch.Tensor.cuda`` and puts the reference on ``sys.path``)."""
+shim patches ``torch.Tensor.cuda`` and puts the reference on ``sys.path``).
+
+``test_shipped_configs_build_this_repos_classes`` needs no reference checkout: the same import swap, the reference's
+shipped JSON configs (stored under ``tests/golden/reference_configs/``) resolved by name the way its ``load_model`` /
+``load_loss`` do, and a CE-only training step of the resulting model and loss on CPU."""
 import json
 import os
 import subprocess
@@ -17,7 +21,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference"
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present (GPU box)")
+CONFIGS = os.path.join(ROOT, "tests", "golden", "reference_configs")
 
 SCRIPT = r"""
 import json, os, sys, types
@@ -140,6 +144,7 @@ _print("RESULT " + json.dumps(out))
 """
 
 
+@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present (GPU box)")
 @pytest.mark.timeout(600)
 def test_reference_manager_builds_and_steps_this_repos_classes():
     env = dict(os.environ, OMP_NUM_THREADS="4")
@@ -168,3 +173,98 @@ def test_reference_manager_builds_and_steps_this_repos_classes():
     assert out["step_loss_vals"] == ["CrossEntropyLoss"]
     assert out["step_grads"] is True
     assert "no CPU fallback" in out["cpu_dc"]                                                    # fails loudly, by design
+
+
+def _swapped_namespace(monkeypatch):
+    """The names `from models import *` / `from losses import *` give the reference's BaseManager after the import swap of
+    INTEGRATION.md section A (modules `models` / `losses` = this repo's packages, as in SCRIPT)."""
+    import types
+    import mscs_amd  # noqa: F401
+    import mscs_amd.losses
+    import mscs_amd.models
+    for name, pkg in (("models", mscs_amd.models), ("losses", mscs_amd.losses)):
+        mod = types.ModuleType(name)
+        pub = [k for k in vars(pkg) if not k.startswith("_")]
+        for k in pub:
+            setattr(mod, k, getattr(pkg, k))
+        mod.__all__ = [k for k in pub if not isinstance(getattr(pkg, k), types.ModuleType)]
+        monkeypatch.setitem(sys.modules, name, mod)
+    ns = {}
+    exec("from models import *\nfrom losses import *", ns)
+    return ns
+
+
+def _shipped(name, patch=None):
+    with open(os.path.join(CONFIGS, name)) as f:
+        cfg = json.load(f)
+    cfg["graph"]["pretrained"] = False
+    if patch:
+        patch(cfg)
+    dataset, experiment = cfg["data"]["dataset"], cfg["data"]["experiment"]
+    cfg["graph"]["dataset"] = dataset
+    cfg["loss"].update({"dataset": dataset, "experiment": experiment, "device": "cpu"})
+    return cfg, experiment
+
+
+def _build(ns, cfg, experiment):
+    # the reference's load_model / load_loss: globals()[name](config=graph, experiment=...) and globals()[name](loss config)
+    model = ns[cfg["graph"]["model"]](config=cfg["graph"], experiment=experiment)
+    loss = ns[cfg["loss"]["name"]](cfg["loss"])
+    return model, loss
+
+
+@pytest.mark.timeout(600)
+def test_shipped_configs_build_this_repos_classes(monkeypatch):
+    import torch
+    ns = _swapped_namespace(monkeypatch)
+    for n in ("HRNet", "UPerNet", "LossWrapper", "DenseContrastiveLossV2_ms", "DenseContrastiveLossV2", "TwoScaleLoss"):
+        assert ns[n].__module__.startswith(("mscs_amd.", "eccv2022")), (n, ns[n].__module__)
+
+    # 1. the shipped HRNet contrastive config
+    model, loss = _build(ns, *_shipped("hrnet_contrastive_CTS.json"))
+    assert type(model).__module__.endswith("models.HRNet") and type(model).__name__ == "HRNet"
+    assert type(loss).__module__.endswith("losses.LossWrapper") and type(loss).__name__ == "LossWrapper"
+    assert list(loss.loss_classes) == ["CrossEntropyLoss", "DenseContrastiveLossV2_ms"]                # config order kept
+    assert type(loss.loss_classes["DenseContrastiveLossV2_ms"]).__module__.endswith("losses.DenseContrastiveLossV2_ms")
+    assert dict(loss.loss_weightings) == {"CrossEntropyLoss": 1, "DenseContrastiveLossV2_ms": 0.1}
+    assert model.projector_model is not None                                  # the reference's return_features
+    params = sum(p.numel() for p in model.parameters())
+    assert params == 70391203 or abs(params - 70.39e6) < 0.05e6                                       # SURVEY row a12
+    dc = loss.loss_classes["DenseContrastiveLossV2_ms"]
+    assert {"scales": dc.scales, "weights": list(dc.weights), "cross": bool(dc.cross_scale_contrast),
+            "K": dc.DCV2_scale0.num_all_classes} == {"scales": 4, "weights": [1, 0.7, 0.4, 0.1], "cross": True, "K": 20}
+    del model, loss
+
+    # 2. the shipped UPerNet + Swin-T config
+    model, loss = _build(ns, *_shipped("upnswin_contrastive_ADE20K.json"))
+    assert type(model).__module__.endswith("models.UPerNet") and type(model).__name__ == "UPerNet"
+    assert "DenseContrastiveLossV2_ms" in loss.loss_classes
+    assert abs(sum(p.numel() for p in model.parameters()) - 62.4e6) < 0.5e6                           # SURVEY row a13
+    del model, loss
+
+    # 3. a CE-only training step of the HRNet config (hrnet18) on CPU, as the reference's forward_step drives it; the
+    #    contrastive loss has no CPU path by design -- it raises, which is checked too
+    def small(cfg):
+        cfg["graph"]["backbone"] = "hrnet18"
+        cfg["loss"]["losses"] = {"CrossEntropyLoss": 1}
+    model, loss = _build(ns, *_shipped("hrnet_contrastive_CTS.json", small))
+    model.train()
+    g = torch.Generator().manual_seed(0)
+    img = torch.randn(2, 3, 64, 64, generator=g)
+    lbl = torch.randint(0, 20, (2, 64, 64), generator=g)
+    output, feats = model(img.float())
+    total = loss(output, lbl.long(), deep_features=feats, epoch=0)
+    total.backward()
+    assert list(output.shape) == [2, 19, 64, 64]
+    assert [list(f.shape) for f in feats] == [[2, 256, 16, 16], [2, 256, 8, 8], [2, 256, 4, 4], [2, 256, 2, 2]]
+    assert total.item() == total.item() and total.item() > 0
+    assert sorted(loss.loss_vals) == ["CrossEntropyLoss"]
+    assert all(p.grad is not None for k, p in model.named_parameters() if not k.startswith("projector_model"))
+
+    def with_dc(cfg):
+        small(cfg)
+        cfg["loss"]["losses"] = {"CrossEntropyLoss": 1, "DenseContrastiveLossV2_ms": 0.1}
+    model, loss = _build(ns, *_shipped("hrnet_contrastive_CTS.json", with_dc))
+    output, feats = model.train()(img.float())
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        loss(output, lbl.long(), deep_features=feats, epoch=0)

@@ -10,9 +10,9 @@ for C in 4 5; do
   mv $OUT/config${C}_kernels.csv $OUT/r04_config${C}_kernels.csv; rm -f $OUT/config${C}_kernel_trace.csv
 done
 cd $ROOT
-python3 bench.py --kernel-table $OUT/r04_kernel_table.json > $OUT/r04_bench_default.json 2> $OUT/bench_default.err
-python3 bench.py --workload loss --steps 30 --warmup 5 > $OUT/r04_bench_loss.json 2> /dev/null
-python3 bench.py --labels blocky --no-cpu-baseline > $OUT/r04_bench_blocky.json 2> /dev/null
-python3 bench.py --config 4 --steps 8 --warmup 3 --no-cpu-baseline --no-eager-step > $OUT/r04_bench_config4.json 2> /dev/null
-python3 bench.py --config 5 --steps 5 --warmup 2 --no-cpu-baseline --no-eager-step > $OUT/r04_bench_config5.json 2> /dev/null
+python3 bench.py --full --kernel-table $OUT/r04_kernel_table.json > $OUT/r04_bench_default.json 2> $OUT/bench_default.err
+python3 bench.py --full --workload loss --steps 30 --warmup 5 > $OUT/r04_bench_loss.json 2> /dev/null
+python3 bench.py --full --labels blocky --no-cpu-baseline > $OUT/r04_bench_blocky.json 2> /dev/null
+python3 bench.py --full --config 4 --steps 8 --warmup 3 --no-cpu-baseline --no-eager-step > $OUT/r04_bench_config4.json 2> /dev/null
+python3 bench.py --full --config 5 --steps 5 --warmup 2 --no-cpu-baseline --no-eager-step > $OUT/r04_bench_config5.json 2> /dev/null
 for f in default loss blocky config4 config5; do python3 -c "import json,sys; d=json.loads(open('$OUT/r04_bench_$f.json').read().strip().splitlines()[-1]); print('$f', d['ms_per_step'], d['value'])"; done

@@ -4,7 +4,7 @@
 # on one box:   gpurun -- bash tools/probes/ab_packed.sh
 cd ${GRAFT_REPO_ROOT:-.}
 P=$PWD/tools/probes/variants/libdcl_packed.so
-one() { python bench.py --steps $1 --warmup 3 --no-cpu-baseline --no-eager-step "${@:2}" 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d.get('contrastive_loss_fwd_bwd_ms'))"; }
+one() { python bench.py --full --steps $1 --warmup 3 --no-cpu-baseline --no-eager-step "${@:2}" 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d.get('contrastive_loss_fwd_bwd_ms'))"; }
 for i in 1 2; do
   for what in "--workload loss" "--config 4" "--config 5"; do
     echo "unpacked $what: $(one 10 $what)"
