@@ -29,7 +29,7 @@ from ..debug import cfg as _dbg
 from ..utils import DATASETS_INFO, printlog
 from .Projector import Projector
 from .ops import (ConvPackGroup, DirectConv2d, GradToken, LazyConcat, conv3x3_over_upsampled, use_gemm_conv1x1,
-                  head_norm_classifier, head_norm_classifier_ok,
+                  head_norm_classifier, head_norm_classifier_ok, has_forward_hooks, note_head_norm_statistics,
                   upsample_bilinear, use_direct_conv3x3, use_direct_conv1x1, upsample_concat, fan_out)
 from .amax import record_stream as _amax_record_stream
 from .fused_bn import FusedBatchNorm2d, bn_act, bn_act_group, can_group, can_group_static
@@ -99,9 +99,10 @@ def _side_streams(device, n):
 
 def _defers(bn, z, conv):
     """conv(relu(bn(z))) without the normalised tensor: the norm is a fused one on its training path and the convolution
-    says it applies the map itself (DirectConv2d.fuses_input_norm)."""
+    says it applies the map itself (DirectConv2d.fuses_input_norm).  Not with forward hooks on either module: the norm's hook would
+    receive the alias that holds z, the convolution's pre-hook the same."""
     return (isinstance(bn, FusedBatchNorm2d) and isinstance(conv, DirectConv2d) and bn._fusable(z, None)
-            and conv.fuses_input_norm(z))
+            and not has_forward_hooks(bn, conv) and conv.fuses_input_norm(z))
 
 
 class BasicBlock(nn.Module):
@@ -685,8 +686,11 @@ class HRNet(nn.Module):
         into one GEMM on z with rescaled weights when the norm is on its fused training path (models/ops_head.py)."""
         bn, cls = self.cls_head[1], self.cls_head[2]
         if len(self.cls_head) == 3 and head_norm_classifier_ok(z, bn, cls):
-            return head_norm_classifier(z, bn, cls)
-        return cls(bn(z))
+            out = head_norm_classifier(z, bn, cls)
+        else:
+            out = cls(bn(z))
+        note_head_norm_statistics(bn)
+        return out
 
     def forward(self, x):
         size = x.shape[-2:]

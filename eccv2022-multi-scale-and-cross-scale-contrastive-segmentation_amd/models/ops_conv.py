@@ -241,6 +241,10 @@ class _Conv3x3Direct(torch.autograd.Function):
         out = torch.empty((x.shape[0], weight.shape[0], (x.shape[2] - 1) // st + 1, (x.shape[3] - 1) // st + 1),
                           dtype=torch.float32, device=x.device)
         pre = pre_of(x)
+        if pre is None and getattr(x, "_dcl_pre", None) is not None:
+            # the alias (or the norm input it shares storage with) was modified in place after the norm: the map no longer
+            # describes its values, and the plain branches below would convolve the raw input z as if it were relu(bn(z))
+            raise RuntimeError("DirectConv2d: a deferred norm output was modified in place after the norm (stale PreAct mark)")
         ctx.pre = pre is not None
         if pre is not None:
             # x's storage holds the raw input z of the norm in front of this convolution; the operand is relu(z sc + sh), formed

@@ -208,3 +208,184 @@ def test_ddp_hrnet48_direct_kernels_and_branch_streams_two_ranks_one_gpu(tmp_pat
     # (DCL_TEST_BACKEND=nccl, a node with two GPUs) the host never waits; gloo -- the stand-in on one-GPU boxes -- completes
     # every collective on the host
     assert a["syncbn_host_waits"] == (0 if a["backend"] == "nccl" else a["syncbn_collectives"])
+
+
+def _rank_setup(rank, world, port, backend):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    import mscs_amd  # noqa: F401
+    dev = torch.device("cuda", _device_of(rank, backend))
+    torch.cuda.set_device(dev)
+    dist.init_process_group(backend, rank=rank, world_size=world)
+    return dev
+
+
+_PRE_SHAPE, _PRE_CO = (4, 32, 16, 32), 48
+
+
+def _pre_inputs():
+    g = torch.Generator().manual_seed(11)
+    n, c, h, w = _PRE_SHAPE
+    x = torch.randn(_PRE_SHAPE, generator=g) * 1.3 + 2.0 * torch.randn(1, c, 1, 1, generator=g)
+    x[:2] += 0.5                                        # the two halves differ: per-rank statistics are not the global ones
+    gamma = torch.rand(c, generator=g) + 0.5
+    gamma[::5] *= -1.0
+    beta = torch.randn(c, generator=g) * 0.5
+    beta[3::7] += 3.0                                   # relu(sh) >> 0 on these channels: the zero border must stay zero
+    wt = torch.randn(_PRE_CO, c, 3, 3, generator=g) * (2.0 / (9 * c)) ** 0.5
+    gy = torch.randn(n, _PRE_CO, h, w, generator=g)
+    return x, gamma, beta, wt, gy
+
+
+def _pre_worker(rank, world, port, out_dir, backend):
+    """deferred FusedBatchNorm2d(sync=True) -> PRE DirectConv2d 3x3 on this rank's half: the launch sequence
+    dcl_bn_stats_minmax_part -> all-reduce -> dcl_bn_finalize_pre with this rank's extrema"""
+    dev = _rank_setup(rank, world, port, backend)
+    from mscs_amd.models.amax import pre_of
+    from mscs_amd.models.fused_bn import FusedBatchNorm2d
+    from mscs_amd.models.ops import DirectConv2d
+    x, gamma, beta, wt, gy = _pre_inputs()
+    c = x.shape[1]
+    half = slice(2 * rank, 2 * rank + 2)
+    bn = FusedBatchNorm2d(c).to(dev)
+    bn.sync = True
+    conv = DirectConv2d(c, _PRE_CO, 3, padding=1, bias=False).to(dev)
+    with torch.no_grad():
+        bn.weight.copy_(gamma); bn.bias.copy_(beta); conv.weight.copy_(wt)
+    xi = x[half].to(dev).requires_grad_(True)
+    assert conv.fuses_input_norm(xi)
+    y = bn(xi, relu=True, defer=True)
+    pre = pre_of(y)
+    assert pre is not None and y.data_ptr() == xi.data_ptr()
+    out = conv(y)
+    out.backward(gy[half].to(dev))
+    c4 = (1, c, 1, 1)
+    mapped = torch.addcmul(pre.sh.view(c4).double(), xi.detach().double(), pre.sc.view(c4).double()).float().relu_()
+    torch.save({"y": out.detach().cpu(), "dx": xi.grad.cpu(), "dgamma": bn.weight.grad.cpu(), "dbeta": bn.bias.grad.cpu(),
+                "dw": conv.weight.grad.cpu(), "rm": bn.running_mean.cpu(), "rv": bn.running_var.cpu(),
+                "amax": pre.amax.max().item(), "amax_want": mapped.max().item()}, os.path.join(out_dir, f"pre{rank}.pt"))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def _close(got, want, bar=2e-5):
+    return (got.double() - want).abs().max().item() <= bar * max(want.abs().max().item(), 1e-12)
+
+
+@pytest.mark.timeout(300)
+def test_deferred_sync_bn_into_pre_convolution_two_ranks(tmp_path):
+    """Two ranks, each with half the batch, against the full-batch float64 composition conv3x3(relu(bn(x))): output and input
+    gradient of each half, running statistics at 2e-5 of max; the ranks' gradients of gamma, beta and the convolution weight add up
+    to the full-batch ones; the absmax of each rank's mapped half exact."""
+    port = _free_port()
+    mp.spawn(_pre_worker, args=(2, port, str(tmp_path), _backend()), nprocs=2, join=True)
+    x, gamma, beta, wt, gy = _pre_inputs()
+    c = x.shape[1]
+    bn = torch.nn.BatchNorm2d(c).double()
+    with torch.no_grad():
+        bn.weight.copy_(gamma); bn.bias.copy_(beta)
+    w64 = wt.double().requires_grad_(True)
+    xr = x.double().requires_grad_(True)
+    y = torch.nn.functional.conv2d(torch.relu(bn(xr)), w64, None, 1, 1)
+    y.backward(gy.double())
+    outs = [torch.load(os.path.join(str(tmp_path), f"pre{q}.pt")) for q in range(2)]
+    for q in range(2):
+        half = slice(2 * q, 2 * q + 2)
+        assert _close(outs[q]["y"], y.detach()[half]), ("y", q)
+        assert _close(outs[q]["dx"], xr.grad[half]), ("dx", q)
+        assert _close(outs[q]["rm"], bn.running_mean) and _close(outs[q]["rv"], bn.running_var), ("running statistics", q)
+        assert outs[q]["amax"] == outs[q]["amax_want"], q
+    for key, want in (("dgamma", bn.weight.grad), ("dbeta", bn.bias.grad), ("dw", w64.grad)):
+        assert _close(outs[0][key] + outs[1][key], want), key
+
+
+_HEAD_SHAPE, _HEAD_K = (4, 37, 6, 12), 19
+
+
+def _head_inputs(r):
+    g = torch.Generator().manual_seed(13)
+    n, c, h, w = _HEAD_SHAPE
+    std = torch.rand(1, c, 1, 1, generator=g) + 0.5
+    z = torch.randn(_HEAD_SHAPE, generator=g) * std + r * std * torch.where(torch.rand(1, c, 1, 1, generator=g) < 0.5, -1.0, 1.0)
+    z[:2] += 0.3 * std                                  # the halves differ
+    gl = torch.randn(n, _HEAD_K, h, w, generator=g) * 1e-3
+    wt = torch.randn(_HEAD_K, c, 1, 1, generator=g) * (1.0 / c) ** 0.5
+    gamma = torch.rand(c, generator=g) + 0.5
+    gamma[::7] *= -1.0
+    beta = torch.randn(c, generator=g) * 0.3
+    return z, gl, wt, gamma, beta
+
+
+_HEAD_RATIOS = (0.3, 30.0)
+
+
+def _head_worker(rank, world, port, out_dir, backend):
+    """HRNet._head_tail with bn.sync = True on this rank's half: one warm-up call (the guard sees the layer's running statistics),
+    then forward + backward; at r = 0.3 the fold (all-reduced statistics and channel sums, per-rank dgamma / dbeta / dW), at r = 30
+    the unfolded SyncBatchNorm -- the same decision on both ranks"""
+    dev = _rank_setup(rank, world, port, backend)
+    import importlib
+    import types
+    from mscs_amd.models.fused_bn import FusedBatchNorm2d
+    from mscs_amd.models.ops import DirectConv2d
+    H = importlib.import_module("mscs_amd.models.HRNet")
+    half = slice(2 * rank, 2 * rank + 2)
+    res = {}
+    for r in _HEAD_RATIOS:
+        z, gl, wt, gamma, beta = _head_inputs(r)
+        c = z.shape[1]
+        bn = FusedBatchNorm2d(c).to(dev)
+        bn.sync = True
+        cls = DirectConv2d(c, _HEAD_K, 1, bias=False).to(dev)
+        with torch.no_grad():
+            bn.weight.copy_(gamma); bn.bias.copy_(beta); cls.weight.copy_(wt)
+            bn.running_mean.copy_(z.double().mean((0, 2, 3)).float()); bn.running_var.copy_(z.double().var((0, 2, 3)).float())
+        head = types.SimpleNamespace(cls_head=torch.nn.Sequential(torch.nn.Identity(), bn, cls).train())
+        zi = z[half].to(dev)
+        with torch.no_grad():
+            H.HRNet._head_tail(head, zi)                # warm-up
+        rm0, rv0 = bn.running_mean.cpu(), bn.running_var.cpu()
+        zf = zi.clone().requires_grad_(True)
+        out = H.HRNet._head_tail(head, zf)
+        node = type(out.grad_fn).__name__
+        out.backward(gl[half].to(dev))
+        res[r] = {"node": node, "y": out.detach().cpu(), "dz": zf.grad.cpu(), "dgamma": bn.weight.grad.cpu(),
+                  "dbeta": bn.bias.grad.cpu(), "dw": cls.weight.grad.cpu(), "rm0": rm0, "rv0": rv0,
+                  "rm": bn.running_mean.cpu(), "rv": bn.running_var.cpu()}
+    torch.save(res, os.path.join(out_dir, f"head{rank}.pt"))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.timeout(300)
+def test_folded_head_sync_bn_two_ranks(tmp_path):
+    """Two ranks against the full-batch float64 conv1x1(bn(z)): logits and dz of each half and the running statistics at 2e-5 of
+    max; dgamma, dbeta and dW of the two ranks add up to the full-batch ones.  Both ranks take the same path: the fold at
+    r = |mean| / std = 0.3, the unfolded norm at r = 30 (ops_head.FOLD_MAX_MEAN_RATIO)."""
+    port = _free_port()
+    mp.spawn(_head_worker, args=(2, port, str(tmp_path), _backend()), nprocs=2, join=True)
+    outs = [torch.load(os.path.join(str(tmp_path), f"head{q}.pt")) for q in range(2)]
+    for r in _HEAD_RATIOS:
+        nodes = [outs[q][r]["node"] for q in range(2)]
+        assert nodes[0] == nodes[1], (r, nodes)
+        assert (nodes[0] == "_HeadNormClassifierBackward") == (r < 1), (r, nodes)
+        z, gl, wt, gamma, beta = _head_inputs(r)
+        c = z.shape[1]
+        assert torch.equal(outs[0][r]["rm0"], outs[1][r]["rm0"]) and torch.equal(outs[0][r]["rv0"], outs[1][r]["rv0"])
+        bn = torch.nn.BatchNorm2d(c).double()
+        conv = torch.nn.Conv2d(c, _HEAD_K, 1, bias=False).double()
+        with torch.no_grad():
+            bn.weight.copy_(gamma); bn.bias.copy_(beta); conv.weight.copy_(wt)
+            bn.running_mean.copy_(outs[0][r]["rm0"]); bn.running_var.copy_(outs[0][r]["rv0"])
+        zr = z.double().requires_grad_(True)
+        y = conv(bn(zr))
+        y.backward(gl.double())
+        for q in range(2):
+            half = slice(2 * q, 2 * q + 2)
+            o = outs[q][r]
+            assert _close(o["y"], y.detach()[half]), ("logits", r, q)
+            assert _close(o["dz"], zr.grad[half]), ("dz", r, q)
+            assert _close(o["rm"], bn.running_mean) and _close(o["rv"], bn.running_var), ("running statistics", r, q)
+        for key, want in (("dgamma", bn.weight.grad), ("dbeta", bn.bias.grad), ("dw", conv.weight.grad)):
+            assert _close(outs[0][r][key] + outs[1][r][key], want), (key, r)

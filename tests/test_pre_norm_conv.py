@@ -328,3 +328,191 @@ def test_a_deferred_norm_output_is_refused_by_everything_but_its_consumer(dev):
     assert torch.equal(out, ref)
     for a, b in zip(bn.buffers(), bn_w.buffers()):
         assert torch.equal(a, b)
+
+
+def test_a_stale_deferred_mark_is_refused(dev):
+    """A deferred norm output whose storage (the norm's input z) was modified in place after the norm: its map no longer describes
+    its values.  Both DirectConv2d forms must raise instead of convolving the raw z as if it were relu(bn(z))."""
+    from mscs_amd.models.fused_bn import FusedBatchNorm2d
+    from mscs_amd.models.ops import DirectConv2d
+    bn = FusedBatchNorm2d(32).to(dev)
+    conv3 = DirectConv2d(32, 32, 3, padding=1, bias=False).to(dev)
+    conv1 = DirectConv2d(32, 32, 1, bias=False).to(dev)
+    for modify in ("z", "y"):
+        z = torch.randn(2, 32, 8, 16, device=dev)
+        assert conv3.fuses_input_norm(z)
+        y = bn(z, relu=True, defer=True)
+        (z if modify == "z" else y).mul_(2.0)
+        for conv in (conv3, conv1):
+            with pytest.raises(RuntimeError):
+                conv(y)
+
+
+def test_forward_hook_on_a_deferred_norm_sees_the_written_tensor(dev):
+    """A forward hook on a BasicBlock's bn1 (and a forward-pre hook on its conv2) receives what the non-deferred path writes, bitwise,
+    and the block's output is bitwise that of the block without hooks: a hooked norm is not deferred (HRNet._defers)."""
+    import importlib
+    from mscs_amd.models import fused_bn
+    from mscs_amd.models.fused_bn import FusedBatchNorm2d
+    from mscs_amd.models.ops import use_direct_conv3x3
+    H = importlib.import_module("mscs_amd.models.HRNet")
+    torch.manual_seed(5)
+    blk = H.BasicBlock(48, 48, norm_layer=FusedBatchNorm2d).to(dev)
+    use_direct_conv3x3(blk)
+    x = torch.randn(2, 48, 32, 64, device=dev).relu_()
+    state = {k: v.clone() for k, v in blk.state_dict().items()}
+    n0 = fused_bn.DEFERRED["count"]
+    plain = blk(x)
+    assert fused_bn.DEFERRED["count"] == n0 + 1                      # without hooks: deferred
+    blk.load_state_dict(state)
+    # what the non-deferred path writes: the same layers, bn1 applied
+    bn1_out = H.bn_act(blk.bn1, blk.conv1(x)).detach().clone()
+    blk.load_state_dict(state)
+    seen = {}
+    h1 = blk.bn1.register_forward_hook(lambda m, i, o: seen.__setitem__("bn1", o.detach().clone()))
+    h2 = blk.conv2.register_forward_pre_hook(lambda m, i: seen.__setitem__("conv2", i[0].detach().clone()))
+    try:
+        out = blk(x)
+    finally:
+        h1.remove()
+        h2.remove()
+    assert fused_bn.DEFERRED["count"] == n0 + 1                      # hooked: written
+    assert torch.equal(seen["bn1"], bn1_out) and torch.equal(seen["conv2"], bn1_out)
+    assert torch.equal(out, plain)
+
+
+# (n, Cin, Cout, H, W, stride), input sizes: every shape the HRNet-W48 benchmark step (12 x 3 x 512 x 1024) runs through the PRE
+# kernels (dcl_conv3x3_pre_f16x3 / dcl_wgrad3x3_pre_f16x3): the BasicBlocks' conv2 on the four branches, the Bottlenecks' conv2
+# (layer 1), the stem's conv2, and the second and third convolutions of the fuse layers' stride-2 chains (0 -> 2, 0 -> 3, 1 -> 3)
+AT_SIZE_SHAPES = [(12, 48, 48, 128, 256, 1), (12, 96, 96, 64, 128, 1), (12, 192, 192, 32, 64, 1), (12, 384, 384, 16, 32, 1),
+                  (12, 64, 64, 128, 256, 1), (12, 64, 64, 256, 512, 2), (12, 48, 48, 64, 128, 2), (12, 48, 192, 64, 128, 2),
+                  (12, 48, 384, 32, 64, 2), (12, 96, 384, 32, 64, 2)]
+
+
+def test_pre_shape_list_is_complete(dev, monkeypatch):
+    """AT_SIZE_SHAPES is every (Cin, Cout, H, W, stride) that one forward + backward of an HRNet-W48 at 512 x 1024 sends to the PRE
+    kernels: a shape that falls off the list would go untested against float64 at its size."""
+    import importlib
+    from mscs_amd import _lib
+    H = importlib.import_module("mscs_amd.models.HRNet")
+    L = _lib.lib()
+    seen = set()
+    conv, wgrad = L.dcl_conv3x3_pre_f16x3, L.dcl_wgrad3x3_pre_f16x3
+
+    def rec_conv(*a):
+        seen.add((a[2], a[6], a[3], a[4], a[14]))
+        return conv(*a)
+
+    def rec_wgrad(*a):
+        seen.add((a[3], a[4], a[5], a[6], a[13]))
+        return wgrad(*a)
+    monkeypatch.setattr(L, "dcl_conv3x3_pre_f16x3", rec_conv, raising=False)
+    monkeypatch.setattr(L, "dcl_wgrad3x3_pre_f16x3", rec_wgrad, raising=False)
+    graph = {"backbone": "hrnet48", "pretrained": False, "dataset": "CITYSCAPES", "align_corners": True}
+    torch.manual_seed(0)
+    m = H.HRNet(graph, 1).to(dev).train()
+    img = torch.randn(1, 3, 512, 1024, device=dev)
+    out = m(img)
+    (out if torch.is_tensor(out) else out[0]).square().mean().backward()
+    torch.cuda.synchronize()
+    assert seen == {s[1:] for s in AT_SIZE_SHAPES}, sorted(seen)
+
+
+def _pre_at_size_inputs(n, c, h, w, r, dev, seed):
+    """z with per-channel means r x std, negative gamma on every fifth channel, beta >> 0 on some (a border padded with relu(sh)
+    instead of 0 would show); running mean = the data's channel means + a small offset (the pivoted regime of a trained network)."""
+    g = torch.Generator(device=dev).manual_seed(seed)
+    std = torch.rand(1, c, 1, 1, device=dev, generator=g) + 0.5
+    sign = torch.where(torch.rand(1, c, 1, 1, device=dev, generator=g) < 0.5, -1.0, 1.0)
+    z = torch.randn(n, c, h, w, device=dev, generator=g) * std + sign * r * std
+    gamma = torch.rand(c, device=dev, generator=g) + 0.5
+    gamma[::5] *= -1.0
+    beta = torch.randn(c, device=dev, generator=g) * 0.5
+    beta[3::7] += 4.0
+    zd = z.double()
+    rmean = (zd.mean((0, 2, 3)) + 0.01 * std.view(c).double()).float()
+    rvar = zd.var((0, 2, 3)).float()
+    return z, gamma, beta, rmean, rvar
+
+
+@pytest.mark.parametrize("r", [0.5, 20.0, 200.0])
+@pytest.mark.parametrize("shape", AT_SIZE_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_pre_kernels_at_benchmark_size_against_fp64(dev, shape, r):
+    """The deferred norm + PRE convolution at the benchmark's sizes against float64, channel means up to 200 std:
+    (a) dcl_conv3x3_pre_f16x3 / dcl_wgrad3x3_pre_f16x3 against the float64 convolution / weight gradient of relu(z sc + sh) (the
+    kernel's own fp32 map promoted), 5e-6 of max; (b) the map: mean, invstd, sc, sh and the running statistics against float64 batch
+    statistics (sh to k 2^-24 (|beta| + |mean sc|), k = 8), the absmax slots exactly max relu(fma(z, sc, sh)); (c) at r = 0.5 the
+    forward against conv(relu(bn64(z))), 5e-6.  Full batch at r = 0.5, two images at r = 20 / 200."""
+    from mscs_amd import _lib as P
+    from mscs_amd.models.amax import pre_of
+    from mscs_amd.models.fused_bn import FusedBatchNorm2d
+    from mscs_amd.models.ops import DirectConv2d
+    import torch.nn.functional as F
+    L = P.lib()
+    n, ci, co, h, w, st = shape
+    if r > 1:
+        n = 2
+    z, gamma, beta, rmean, rvar = _pre_at_size_inputs(n, ci, h, w, r, dev, seed=ci + h + st)
+    eps, mom = 1e-5, 0.1
+    # (b) the map: statistics + finalisation as the deferred norm runs them
+    sc, sh, amax, mean, invstd, rm, rv, nbt, mm, ns = _deferred(L, P, z, gamma, beta, rmean, rvar, eps, mom)
+    zd = z.double()
+    m64 = zd.mean((0, 2, 3))
+    v64 = zd.var((0, 2, 3), unbiased=False)
+    is64 = 1.0 / torch.sqrt(v64 + eps)
+    sc64 = gamma.double() * is64
+    sh64 = beta.double() - m64 * sc64
+    u = 2.0 ** -24
+    cnt = n * h * w
+    errs = {"mean": ((mean.double() - m64).abs() / (m64.abs() + v64.sqrt())).max().item() / u,
+            "invstd": ((invstd.double() - is64).abs() / is64).max().item() / u,
+            "sc": ((sc.double() - sc64).abs() / sc64.abs()).max().item() / u,
+            "sh": ((sh.double() - sh64).abs() / (beta.double().abs() + (m64 * sc64).abs())).max().item() / u,
+            "running_mean": ((rm.double() - ((1 - mom) * rmean.double() + mom * m64)).abs()
+                             / (m64.abs() + v64.sqrt())).max().item() / u,
+            "running_var": ((rv.double() - ((1 - mom) * rvar.double() + mom * v64 * cnt / (cnt - 1))).abs()
+                            / rv.double()).max().item() / u}
+    print(shape, r, {k: round(v, 2) for k, v in errs.items()})
+    for k, v in errs.items():
+        assert v <= 8, (k, v)
+    a = torch.addcmul(sh.view(1, ci, 1, 1).double(), zd, sc.view(1, ci, 1, 1).double()).float().relu_()     # one rounding: an fma
+    amax_want = a.max().item()
+    assert amax.max().item() == amax_want
+    del a
+    # (a) the operator, through the modules: FusedBatchNorm2d(defer=True) -> DirectConv2d
+    bn = FusedBatchNorm2d(ci, eps=eps, momentum=mom).to(dev)
+    with torch.no_grad():
+        bn.weight.copy_(gamma); bn.bias.copy_(beta); bn.running_mean.copy_(rmean); bn.running_var.copy_(rvar)
+    conv = DirectConv2d(ci, co, 3, st, 1, bias=False).to(dev)
+    g = torch.Generator(device=dev).manual_seed(1)
+    with torch.no_grad():
+        conv.weight.copy_(torch.randn(co, ci, 3, 3, device=dev, generator=g) * (2.0 / (9 * ci)) ** 0.5)
+    assert conv.fuses_input_norm(z)
+    y = bn(z, relu=True, defer=True)
+    pre = pre_of(y)
+    # the module runs the single-launch dcl_bn_stats_pre on one rank: the same map, absmax and running statistics as checked above
+    assert pre is not None and torch.equal(pre.sc, sc) and torch.equal(pre.sh, sh)
+    assert pre.amax.max().item() == amax_want
+    assert torch.equal(bn.running_mean, rm) and torch.equal(bn.running_var, rv)
+    out = conv(y)
+    ho, wo = out.shape[2:]
+    gy = torch.randn(n, co, ho, wo, device=dev, generator=g) * 1e-3
+    out.backward(gy)
+    w64 = conv.weight.detach().double()
+    gw64 = torch.zeros_like(w64)
+    ey = ymax = ee = 0.0
+    for b in range(n):
+        a64 = torch.relu(zd[b:b + 1] * sc.double().view(1, ci, 1, 1) + sh.double().view(1, ci, 1, 1))
+        y64 = F.conv2d(a64, w64, None, st, 1)
+        gw64 += torch.nn.grad.conv2d_weight(a64, w64.shape, gy[b:b + 1].double(), st, 1)
+        ey = max(ey, (out[b:b + 1].detach().double() - y64).abs().max().item())
+        ymax = max(ymax, y64.abs().max().item())
+        if r < 1:
+            # (c) end to end: the float64 norm of the float64 statistics
+            e64 = torch.relu((zd[b:b + 1] - m64.view(1, ci, 1, 1)) * sc64.view(1, ci, 1, 1) + beta.double().view(1, ci, 1, 1))
+            ee = max(ee, (out[b:b + 1].detach().double() - F.conv2d(e64, w64, None, st, 1)).abs().max().item())
+    ew = (conv.weight.grad.double() - gw64).abs().max().item() / gw64.abs().max().item()
+    print(shape, r, "forward", ey / ymax, "wgrad", ew, "end to end", ee / ymax)
+    assert ey <= 5e-6 * ymax, ("forward", ey / ymax)
+    assert ew <= 5e-6, ("weight gradient", ew)
+    assert ee <= 5e-6 * ymax, ("end to end", ee / ymax)
