@@ -7,6 +7,7 @@
 #include <utility>
 
 #include "dcl_common.h"
+#include "dcl_f16x3.h"      // half8, split2, F16_TARGET, pow2_scale
 
 // launch arguments (one definition for every translation unit that instantiates conv_body)
 struct ConvArgs {
@@ -36,8 +37,6 @@ bool dcl_conv_pre_has_tile(int R, int P, int stride, bool ws2);
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
 // Bound probes (tools/probes/conv_bounds.sh builds the library with -DDCL_CONV_PROBE=<bits>; 0 in the product): 1 = no
 // MFMAs, 2 = no patch loads, 4 = no output stores, 8 = no weight-fragment loads.  Results are wrong, times tell which part
 // of a launch bounds it.
@@ -60,27 +59,6 @@ constexpr int TW = 32;          // tile width in pixels (one MFMA pixel tile = 1
 constexpr int PIXB = 80;        // bytes per LDS pixel record
 
 __device__ __forceinline__ int jrow(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-// Packed f16 pairs (low half = first value) of hi = f16(v * s) and lo = f16(v * s - hi) for two values.  s is a
-// power of two (or 0), so v * s is exact and the fused form is the same number; v_fma_mix{lo,hi}_f16 takes f32 /
-// f16 inputs, computes in f32 and writes one f16 half of the destination: 2 VALU instructions per value, no packing.
-__device__ __forceinline__ void split2(float v0, float v1, float s, unsigned &hi, unsigned &lo)
-{
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(v0), "v"(s));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(v1), "v"(s));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=&v"(lo) : "v"(v0), "v"(s), "v"(hi));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(v1), "v"(s), "v"(hi));
-}
-
-
-constexpr float F16_TARGET = 16384.0f;      // operands are scaled so that their absmax lands in (2^13, 2^14]
-
-// power-of-two operand scale from the tensor's absmax (same expression in the packer and in the convolution, so
-// both see the same weight scale); an all-zero tensor takes 1, inf / nan propagate into the products
-__device__ __forceinline__ float pow2_scale(float amax)
-{
-    return amax == 0.f ? 1.f : exp2f(fminf(fmaxf(floorf(log2f(F16_TARGET / amax)), -100.f), 100.f));
-}
 
 // S = stride (1 | 2).  A stride-2 tile reads a (2 * 4P + 1) x 65 patch, so S = 2 is instantiated with P = 1 only.
 //

@@ -26,6 +26,7 @@
 //
 // Roofline: MFMA; algorithmic FLOP = 2 M N K, issued as 3 f16 passes -> peak 2500 / 3 = 833 TFLOP/s.
 #include "dcl_common.h"
+#include "dcl_f16x3.h"      // split2, pow2_scale, u32x4
 #include <type_traits>
 
 // A/B and bound probes (tools/probes/gemm_ab.sh); the product build leaves them at their defaults
@@ -42,22 +43,6 @@
 #define GEMM_MFMA(A, B, C) ((DCL_GEMM_PROBE & 1) ? (C) : __builtin_amdgcn_mfma_f32_32x32x16_f16((A), (B), (C), 0, 0, 0))
 
 namespace {
-
-constexpr float F16_TARGET_G = 16384.0f;
-
-__device__ __forceinline__ float pow2_scale_g(float amax)
-{
-    return amax == 0.f ? 1.f : exp2f(fminf(fmaxf(floorf(log2f(F16_TARGET_G / amax)), -100.f), 100.f));
-}
-
-// packed f16 pairs of hi = f16(v * s), lo = f16(v * s - hi) for two values (see dcl_conv3x3.hip)
-__device__ __forceinline__ void split2g(float v0, float v1, float s, unsigned &hi, unsigned &lo)
-{
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(v0), "v"(s));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(v1), "v"(s));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=&v"(lo) : "v"(v0), "v"(s), "v"(hi));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(v1), "v"(s), "v"(hi));
-}
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
@@ -155,7 +140,6 @@ __device__ __forceinline__ int slot_of(int r)
 // One thread's share of an operand tile (BX rows x 32 k = BX units of 32 elements; unit u): where it loads from and
 // where it stores to.  All per-k-step address arithmetic is scalar (a uniform base pointer advances; the lane part is a
 // 32-bit byte offset computed once).
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct StageState {
     unsigned voff[8];               // lane byte offsets into the operand (buffer addressing: 32-bit, bounds-checked)
@@ -219,8 +203,8 @@ struct Stager {
                     h = uint2{__float_as_uint(v[j].x), __float_as_uint(v[j].y)};
                     l = uint2{__float_as_uint(v[j].z), __float_as_uint(v[j].w)};
                 } else {
-                    split2g(v[j].x, v[j].y, sj, h.x, l.x);
-                    split2g(v[j].z, v[j].w, sj, h.y, l.y);
+                    split2(v[j].x, v[j].y, sj, h.x, l.x);
+                    split2(v[j].z, v[j].w, sj, h.y, l.y);
                 }
                 if (DCL_GEMM_PROBE & 16) {
                     asm volatile("" ::"v"(h.x), "v"(h.y), "v"(l.x), "v"(l.y));
@@ -234,10 +218,10 @@ struct Stager {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 uint4 h, l;
-                split2g(f[0 * 4 + i], f[1 * 4 + i], s, h.x, l.x);
-                split2g(f[2 * 4 + i], f[3 * 4 + i], s, h.y, l.y);
-                split2g(f[4 * 4 + i], f[5 * 4 + i], s, h.z, l.z);
-                split2g(f[6 * 4 + i], f[7 * 4 + i], s, h.w, l.w);
+                split2(f[0 * 4 + i], f[1 * 4 + i], s, h.x, l.x);
+                split2(f[2 * 4 + i], f[3 * 4 + i], s, h.y, l.y);
+                split2(f[4 * 4 + i], f[5 * 4 + i], s, h.z, l.z);
+                split2(f[6 * 4 + i], f[7 * 4 + i], s, h.w, l.w);
                 char *p = hi + ((i >> 1) ? q.wb : q.wa) + 8 * i * 16;
                 *reinterpret_cast<uint4 *>(p) = h;
                 *reinterpret_cast<uint4 *>(p + 4 * KG * 16) = l;
@@ -297,7 +281,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm(GemmArgs a)
         ma = fmaxf(ma, __shfl_xor(ma, o, 64));
         mb = fmaxf(mb, __shfl_xor(mb, o, 64));
     }
-    const float sa = pow2_scale_g(ma), sb = pow2_scale_g(mb);
+    const float sa = pow2_scale(ma), sb = pow2_scale(mb);
 
     // the operand this wave stages, as a bounds-checked buffer (reads past the last element return 0), and the scalar
     // byte offset of the k-step it loads next

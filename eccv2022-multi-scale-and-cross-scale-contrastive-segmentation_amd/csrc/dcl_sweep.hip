@@ -23,6 +23,7 @@
 #include <unordered_map>
 
 #include "dcl_common.h"
+#include "dcl_f16x3.h"      // half8, u32x4, split2
 
 namespace {
 
@@ -51,7 +52,6 @@ enum { MODE_Z = 0, MODE_POS = 1, MODE_BWD = 2 };
 // K = 2 each) -- 5.3x fewer matrix-pipe cycles; measured |dS| 8.3e-6 vs 7.2e-6 for plain fp32.
 // The dropped lo.lo term is 2^-22 relative.  A bank row in this format is [256 hi | 256 lo] halves = 1 KiB,
 // the same size as the f32 row, so staging and LDS geometry are unchanged.
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef __fp16 fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
 typedef __attribute__((address_space(3))) fp16x4 LDS_FP16X4;
 constexpr int ROWH = 2 * ROWF;          // LDS row stride in halves (1040 B)
@@ -93,6 +93,8 @@ struct SweepArgs {
     int spos_ld;
 };
 
+// (Local, not dcl_f16x3.h's dma16: this is the `... off` form, full 64-bit per-lane addresses instead of scalar base + 32-bit lane
+// offset, and it takes the LDS destination as a pointer.  dma_wait_barrier below also differs: it carries the workgroup barrier.)
 // One LDS-DMA wave-instruction: 64 lanes x 16 B from per-lane global addresses to the wave-uniform LDS address
 // `lds_dst` + lane * 16.  Issued through inline asm ON PURPOSE: hipcc tracks a builtin LDS-DMA as a pending LDS write
 // and puts `s_waitcnt vmcnt(0)` in front of the next ds_read that may alias it -- i.e. directly behind the prefetch,
@@ -141,19 +143,6 @@ __device__ __forceinline__ void stage_chunk_h(float *buf, const _Float16 *Bh, in
 }
 
 __device__ __forceinline__ int jrow(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-// Packed f16 pair (low half = first value) of hi = f16(v * s) and lo = f16(v * s - hi) for two values; s is a power of
-// two, so v * s is exact and the fused form is the same number.  v_fma_mix{lo,hi}_f16: f32 / f16 inputs, f32
-// arithmetic, one f16 half of the destination written -- 2 VALU per value, no separate packing (the compiler's own
-// lowering of the C expression takes 3+ and a v_pack).
-__device__ __forceinline__ void split2(float v0, float v1, float s, unsigned &hi, unsigned &lo)
-{
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(v0), "v"(s));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(v1), "v"(s));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=&v"(lo) : "v"(v0), "v"(s), "v"(hi));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(v1), "v"(s), "v"(hi));
-}
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // LDS operand fetch, software-pipelined by hand: the reads for step q+1 are issued right after the
 // FIRST MFMA of step q, so they land under the remaining MFMAs of that step (sched_group_barrier pins

@@ -23,119 +23,33 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-
-constexpr float F16_TARGET = 16384.0f;
-
-__device__ __forceinline__ float pow2_scale(float amax)
-{
-    return amax == 0.f ? 1.f : exp2f(fminf(fmaxf(floorf(log2f(F16_TARGET / amax)), -100.f), 100.f));
-}
-
-// Packed f16 pair (lo half = element 0) of hi = f16(v * s) and of lo = f16(v * s - hi) for two values.  s is a power
-// of two (or 0), so v * s is exact and the fused form computes the same value; written as v_fma_mix{lo,hi}_f16
-// (f32 / f16 inputs, f32 arithmetic, f16 result into one half of the destination): 2 VALU instructions per value
-// and no packing.  The compiler's own lowering of the C expression takes 3+ and the kernel is VALU-issue-bound.
-__device__ __forceinline__ void split2(float v0, float v1, float s, unsigned &hi, unsigned &lo)
-{
-    // (mixlo leaves the upper half of its destination alone; mixhi fills it right after, so no initialisation)
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(v0), "v"(s));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(v1), "v"(s));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=&v"(lo) : "v"(v0), "v"(s), "v"(hi));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(v1), "v"(s), "v"(hi));
-}
-
-// one value: f16 hi / lo in the low halves of hi / lo (upper halves undefined)
-__device__ __forceinline__ void split1(float v0, float s, unsigned &hi, unsigned &lo)
-{
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(v0), "v"(s));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=&v"(lo) : "v"(v0), "v"(s), "v"(hi));
-}
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ half8 as_half8(u32x4 v) { return __builtin_bit_cast(half8, v); }
-
 // UPS: dy is the gradient of a STRIDE-2 convolution, i.e. the stride-1 formulation sees it zero-inserted at odd
 // coordinates: row y of the virtual dy is row y / 2 of the stored one for even y (else zero), and an octet of 8
 // virtual pixels is 4 stored values interleaved with zeros.
 template <int NCO, int NCI, bool UPS>
 __global__ __launch_bounds__(256, 1) void k_wgrad3x3(WgradArgs a)
 {
+    static_assert(NCO * NCI <= 4, "four tiles per wave at most (six spilled in the main loop)");
     __shared__ float wm[8];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, q4 = lane >> 4, j = lane & 15;
 
-    // operand scales from the producers' partial maxima
     float sx, sg;
-    {
-        float mx = 0.f, mg = 0.f;
-        for (int i = tid; i < a.xcount; i += 256)
-            mx = fmaxf(mx, a.xamax[i]);
-        for (int i = tid; i < a.gcount; i += 256)
-            mg = fmaxf(mg, a.gamax[i]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-            mg = fmaxf(mg, __shfl_xor(mg, o, 64));
-        }
-        if (lane == 0) {
-            wm[wave] = mx;
-            wm[4 + wave] = mg;
-        }
-        __syncthreads();
-        sx = pow2_scale(fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3])));
-        sg = pow2_scale(fmaxf(fmaxf(wm[4], wm[5]), fmaxf(wm[6], wm[7])));
-    }
-    // XCD-aware decode of the 1-D grid: consecutive workgroup ids go round-robin over the 8 XCDs, so
-    // id = xcd + 8 * (pair + npairs * hi) puts every (co group, ci group) pair of one pixel split on the SAME XCD,
-    // next to each other in dispatch order -- they stream the same dy / x rows, which then come out of that
-    // XCD's L2 instead of being fetched once per pair.
+    wgrad_scales(a, wm, sx, sg);
     int pair, xsplit;
     if (a.rect_mode) {
-        // Many tile pairs, one pixel split (large channel counts): every workgroup streams ALL pixels, so what
-        // matters is which workgroups share an L2 while they do.  The (co group x ci group) grid is cut into
-        // rectangles of rect_c x rect_i = 32 pairs -- they read rect_c + rect_i operand row sets instead of 64 --
-        // and rectangle q of XCD k takes the ids k + 8 * (32 q .. 32 q + 31): one XCD (32 CUs), adjacent dispatch
-        // slots.  (Head convolution, 15 x 45 pairs: FETCH_SIZE 28.0 GiB -> 16.5 GiB per launch, 12.9 -> 12.5 ms.)
-        const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-        const int unit = (slot >> 5) * 8 + xcd, idx = slot & 31;       // unit = (pixel split, rectangle)
-        const int ncog = a.npairs / a.ncig, rects_i = (a.ncig + a.rect_i - 1) / a.rect_i;
-        const int nrect = ((ncog + a.rect_c - 1) / a.rect_c) * rects_i;
-        const int rect = unit % nrect;
-        xsplit = unit / nrect;
-        const int cg = (rect / rects_i) * a.rect_c + idx / a.rect_i, ci = (rect % rects_i) * a.rect_i + idx % a.rect_i;
-        if (xsplit >= a.nx || cg >= ncog || ci >= a.ncig)
-            return;                             // padding of the last rectangles (the whole workgroup leaves)
-        pair = cg * a.ncig + ci;
-    } else {
-        const int nx8 = a.nx & ~7, main_blocks = nx8 * a.npairs;
-        if ((int)blockIdx.x < main_blocks) {
-            const int xcd = blockIdx.x & 7, rest = blockIdx.x >> 3;
-            pair = rest % a.npairs;
-            xsplit = (rest / a.npairs) * 8 + xcd;
-        } else {                                // the nx % 8 left-over pixel splits, in plain order
-            const int rest = blockIdx.x - main_blocks;
-            pair = rest % a.npairs;
-            xsplit = nx8 + rest / a.npairs;
-        }
-    }
+        if (!wgrad_decode_rect(a, pair, xsplit))
+            return;
+    } else
+        wgrad_decode_flat(a, pair, xsplit);
     const int split = xsplit * 4 + wave;           // a wave past the last split gets an empty run and adds zeros
     const int cog = pair / a.ncig, cig = pair - cog * a.ncig;
     const int co0 = cog * NCO * 16, ci0 = cig * NCI * 16;
     const size_t plane = (size_t)a.H * a.W;
-    bool ci_ok[NCI];            // the last ci group is ragged when the tile count is not a multiple of NCI
-#pragma unroll
-    for (int u = 0; u < NCI; ++u)
-        ci_ok[u] = ci0 + 16 * u < a.Cin;
+    bool ci_ok[NCI];
+    wgrad_ci_ok(ci_ok, ci0, a.Cin);
 
     f32x4 acc[NCO][NCI][9];
-#pragma unroll
-    for (int t = 0; t < NCO; ++t)
-#pragma unroll
-        for (int u = 0; u < NCI; ++u)
-#pragma unroll
-            for (int k = 0; k < 9; ++k)
-                acc[t][u][k] = f32x4{0.f, 0.f, 0.f, 0.f};
+    DCL_WGRAD_CLEAR(acc, 9);
 
     // this split's share of the flat (image, strip, input row) sequence: rows [t0, t1), walked column by column
     const long long T = (long long)a.units * a.H;              // units = images x strips (columns)
@@ -337,66 +251,9 @@ __global__ __launch_bounds__(256, 1) void k_wgrad3x3(WgradArgs a)
             step(std::integral_constant<int, 4>{}, r + 4);
     }
 
-    // The four waves of a workgroup hold partial sums of the SAME (co, ci) tiles: they are combined through LDS in
-    // a fixed order, (w0 + w1) + (w2 + w3), so that one slab per workgroup (not per wave) goes to memory.
-    // (Only for the variants with <= 3 tiles per tap: with 6 the extra live ranges make the register allocator spill
-    // inside the main loop, so those keep one slab per wave.)
-    constexpr bool LDSRED = NCO * NCI <= 4;
-    if (LDSRED) {
-        constexpr int NREG = LDSRED ? NCO * NCI * 36 : 1;
-        __shared__ float red[2][NREG][64];
-        auto put = [&](int b) {
-#pragma unroll
-            for (int t = 0; t < NCO; ++t)
-#pragma unroll
-                for (int u = 0; u < NCI; ++u)
-#pragma unroll
-                    for (int k = 0; k < 9; ++k)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            red[b][((t * NCI + u) * 9 + k) * 4 + q][lane] = acc[t][u][k][q];
-        };
-        auto add = [&](int b) {
-#pragma unroll
-            for (int t = 0; t < NCO; ++t)
-#pragma unroll
-                for (int u = 0; u < NCI; ++u)
-#pragma unroll
-                    for (int k = 0; k < 9; ++k)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            acc[t][u][k][q] += red[b][((t * NCI + u) * 9 + k) * 4 + q][lane];
-        };
-        if (wave & 1)
-            put(wave >> 1);
-        __syncthreads();
-        if (!(wave & 1))
-            add(wave >> 1);
-        __syncthreads();
-        if (wave == 2)
-            put(0);
-        __syncthreads();
-        if (wave != 0)
-            return;
-        add(0);
-    }
-    else if (split >= a.S)
-        return;
-    // slab [xsplit | split][tap][co][ci]; accumulator register q of lane (q4, j) is (co = 4 q4 + q, ci = j) of its tile
-    const float inv = 1.0f / (sx * sg);
-    float *out = a.part + (size_t)(LDSRED ? xsplit : split) * 9 * a.Cout * a.Cin;
-#pragma unroll
-    for (int t = 0; t < NCO; ++t)
-#pragma unroll
-        for (int u = 0; u < NCI; ++u)
-#pragma unroll
-            for (int k = 0; k < 9; ++k)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int co = co0 + 16 * t + 4 * q4 + q, ci = ci0 + 16 * u + j;
-                    if (ci_ok[u])
-                        out[((size_t)k * a.Cout + co) * a.Cin + ci] = acc[t][u][k][q] * inv;
-                }
+    // one slab per workgroup: [xsplit][tap][co][ci]
+    __shared__ float red[2][NCO * NCI * 36][64];
+    wgrad_reduce_store(acc, red, wave, lane, a.part, xsplit, a.Cout, a.Cin, co0, ci0, ci_ok, q4, j, sx, sg);
 }
 
 // dw[co][ci][tap] = sum_s part[s][tap][co][ci].  Block = 32 outputs x 8 slab groups: group g adds slabs g, g+8, ...
@@ -495,13 +352,6 @@ static int g_variant = -1;     // 0 = MFMA-order operand loads (this file), -1 /
 // loads also serve tensors beyond the DMA kernel's 32-bit offsets and the zero-inserted stride-2 form
 static bool use_dma(int Cin, int H, int W) { return g_variant != 0 && (size_t)Cin * H * W * 4 < ((size_t)1 << 32); }
 
-// dcl_wgrad3x3_s2.hip
-bool dcl_wgrad_s2_supported(int H, int W);
-void dcl_wgrad_s2_set_dma(int on);
-int dcl_wgrad_s2_slabs(int N, int Cin, int Cout, int H, int W, int force_nco, int force_nci);
-void dcl_wgrad_s2_launch(const float *x, const float *dy, int N, int Cin, int Cout, int H, int W, const float *xamax,
-                         int xcount, const float *gamax, int gcount, float *part, int force_nco, int force_nci,
-                         hipStream_t s, int *nslab, const float *pre_sc = nullptr, const float *pre_sh = nullptr);
 static int g_s2_native = 1;     // stride 2: 1 = output-pixel formulation (dcl_wgrad3x3_s2.hip), 0 = zero-inserted dy
 
 static int g_wave_band = 0;     // wave form: rows per column of the traversal (0 = whole strips: the default -- 32-row bands
@@ -510,50 +360,80 @@ static int g_strip_group = 1;   // waves of a workgroup on adjacent strips (Wgra
 static int g_wave_mode = 2;     // 129 .. 256 tile pairs of the (3, 1) tile: pixel splits dealt out to waves (dcl_wgrad3x3d.hip);
                                 // 2 = a workgroup's waves take the same split of four neighbouring pairs, 1 = four splits of a pair
 
-static void wgrad_plan(int N, int Cin, int Cout, int H, int W, int &nco, int &nci, int &S, int &units, bool *wave_mode = nullptr)
+// The one launch plan: every decision between the shape and the launch is taken here, once.
+static WgradPlan wgrad_plan(int N, int Cin, int Cout, int H, int W, int stride)
 {
+    WgradPlan p = {};
+    if (stride == 2 && g_s2_native && dcl_wgrad_s2_supported(H, W)) {
+        dcl_wgrad_s2_plan(N, Cin, Cout, H, W, g_tile_nco, g_tile_nci, p);
+        return p;
+    }
     const int cot = Cout / 16, cit = Cin / 16;
     // Tiles per wave, measured on the HRNet-W48 shapes at batch 12 (tools/wgrad_tiles.py, and bench.py with
     // DCL_WGRAD_TILE: the step decides, the slabs of the larger tiles cost HBM traffic that the standalone timing does not
     // show): three co tiles x one ci tile wherever the co tiles divide by three (48 ... 720 channels: step 122.3 ms
     // against 122.8 with (2, 2) at 192 and (3, 2) at 384 channels); else the four-tile wave (2, 2), (2, 1), (1, 2), (1, 1).
     if (cot % 3 == 0) {
-        nco = 3;
-        nci = 1;
+        p.nco = 3;
+        p.nci = 1;
     } else {
-        nco = (cot % 2 == 0) ? 2 : 1;
-        nci = (cit % 2 == 0) ? 2 : 1;
+        p.nco = (cot % 2 == 0) ? 2 : 1;
+        p.nci = (cit % 2 == 0) ? 2 : 1;
     }
-    if (g_tile_nco > 0 && g_tile_nco <= 3 && cot % g_tile_nco == 0)
-        nco = g_tile_nco;
+    if (g_tile_nco > 0 && cot % g_tile_nco == 0)
+        p.nco = g_tile_nco;
     if (g_tile_nci > 0)
-        nci = g_tile_nci;
-    const int pairs = (cot / nco) * ((cit + nci - 1) / nci);
-    units = N * ((W + 31) / 32);            // columns: (image, 32-pixel strip), H input rows each
+        p.nci = g_tile_nci;
+    if (p.nco * p.nci > 4)      // a forced ci count beside three co tiles: no six-tile wave (as dcl_wgrad_s2_plan)
+        p.nci = 1;
+    const bool dma = stride == 1 && use_dma(Cin > Cout ? Cin : Cout, H, W);
+    p.family = dma && dcl_wgrad_dma_supported(p.nco, p.nci) ? WGRAD_DMA : WGRAD_DIRECT;
+    p.ncig = (cit + p.nci - 1) / p.nci;
+    p.npairs = (cot / p.nco) * p.ncig;
+    p.units = N * ((W + 31) / 32);          // columns: (image, 32-pixel strip), H input rows each
     // One workgroup (4 waves = 4 splits of one pair) per CU is all that fits (a wave owns most of its SIMD's
     // registers): at most 256 workgroups, or the stragglers run as a second round and double the kernel time.
-    int nx = g_wg_target / pairs;
+    int nx = g_wg_target / p.npairs;
     if (g_force_nx > 0)
         nx = g_force_nx;
     if (nx < 1)
         nx = 1;         // more tile pairs than CUs (head convolution): one pixel split; finer splits were tried and
                         // lose (3 splits fill the last round better but take 26 ms against 12.5 ms)
-    S = 4 * nx;
-    if ((long long)S > (long long)units * H)
-        S = units * H;
-    if (wave_mode) {
-        // one workgroup per pair and CUs left over: the splits go to single waves, S = 128 / (pairs of one XCD) of them
-        const int sw = 128 / ((pairs + 7) / 8);
-        *wave_mode = g_wave_mode && g_force_nx == 0 && pairs > 128 && pairs <= 256 && sw > 4 &&
-                     dcl_wgrad_dma_wave_mode_supported(nco, nci) && (long long)sw <= (long long)units * H;
-        if (*wave_mode)
-            S = sw;
+    p.S = 4 * nx;
+    if ((long long)p.S > (long long)p.units * H)
+        p.S = p.units * H;
+    // one workgroup per pair and CUs left over: the splits go to single waves, S = 128 / (pairs of one XCD) of them
+    const int sw = 128 / ((p.npairs + 7) / 8);
+    const bool wm = dma && g_wave_mode && g_force_nx == 0 && p.npairs > 128 && p.npairs <= 256 && sw > 4 &&
+                    dcl_wgrad_dma_wave_mode_supported(p.nco, p.nci) && (long long)sw <= (long long)p.units * H;
+    if (wm)
+        p.S = sw;
+    p.wave_mode = wm ? g_wave_mode : 0;
+    p.band = (wm && g_wave_band > 0 && H % g_wave_band == 0 && H > g_wave_band) ? g_wave_band : H;
+    p.nx = (p.S + 3) / 4;                                    // workgroups per pair (4 splits each)
+    // adjacent strips for the waves of a workgroup (dcl_wgrad3x3d.hip): unclamped split count, strips in fours / pairs
+    p.grp = 1;
+    if (g_strip_group && !wm && p.S == 4 * p.nx && p.S >= 4) {
+        const int strips = (W + 31) / 32;
+        p.grp = (strips % 4 == 0) ? 4 : ((strips % 2 == 0) ? 2 : 1);
     }
+    p.grid = (unsigned)(p.npairs * p.nx);        // exactly the populated workgroups, <= 256 whenever pairs <= 256
+    p.rect_i = p.ncig >= 16 ? 16 : (p.ncig >= 8 ? 8 : (p.ncig >= 4 ? 4 : (p.ncig >= 2 ? 2 : 1)));
+    p.rect_c = 32 / p.rect_i;
+    p.rect_mode = p.npairs > 128 ? 1 : 0;
+    if (p.rect_mode) {
+        const int ncog = p.npairs / p.ncig;
+        const int units_r = ((ncog + p.rect_c - 1) / p.rect_c) * ((p.ncig + p.rect_i - 1) / p.rect_i) * p.nx;
+        p.grid = (unsigned)(((units_r + 7) / 8) * 8 * 32);
+    }
+    p.slabs = wm ? p.S : p.nx;                  // one slab per wave-level split, or per workgroup (4 splits)
+    return p;
 }
 
 extern "C" int dcl_wgrad3x3_set_tile(int nco, int nci)
 {
-    if (nco < 0 || nco > 5 || nco == 4 || nci < 0 || nci > 2 || (nco == 3 && nci == 2))      // (the six-tile wave spilled: retired)
+    // only tiles with an instantiated kernel (the six-tile wave (3, 2) spilled: retired)
+    if (nco < 0 || nco > 3 || nci < 0 || nci > 2 || (nco == 3 && nci == 2))
         return DCL_EINVAL;
     g_tile_nco = nco;
     g_tile_nci = nci;
@@ -612,14 +492,7 @@ extern "C" int dcl_wgrad3x3_splits(int N, int Cin, int Cout, int H, int W, int s
 {
     if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || (Cin & 15) || (Cout & 15) || stride < 1 || stride > 2)
         return 0;
-    if (stride == 2 && g_s2_native && dcl_wgrad_s2_supported(H, W))
-        return dcl_wgrad_s2_slabs(N, Cin, Cout, H, W, g_tile_nco, g_tile_nci);
-    int nco, nci, S, units;
-    bool wm = false;
-    wgrad_plan(N, Cin, Cout, H, W, nco, nci, S, units, stride == 1 && use_dma(Cin > Cout ? Cin : Cout, H, W) ? &wm : nullptr);
-    if (wm)
-        return S;                                  // one slab per wave-level split
-    return nco * nci <= 4 ? (S + 3) / 4 : S;      // one slab per workgroup (4 splits), or per wave (6-tile variant)
+    return wgrad_plan(N, Cin, Cout, H, W, stride).slabs;
 }
 
 static int wgrad3x3_impl(const float *x, const float *dy, int N, int Cin, int Cout, int H, int W, const float *xamax, int xcount,
@@ -639,13 +512,9 @@ extern "C" int dcl_wgrad3x3_pre_supported(int N, int Cin, int Cout, int H, int W
 {
     if (N <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || (Cin & 15) || (Cout & 15) || (W & 7))
         return 0;
-    if (stride == 2)
-        return g_s2_native && dcl_wgrad_s2_supported(H, W) ? 1 : 0;
-    if (stride != 1)
+    if (stride != 1 && stride != 2)
         return 0;
-    int nco, nci, S, units;
-    wgrad_plan(N, Cin, Cout, H, W, nco, nci, S, units);
-    return use_dma(Cin > Cout ? Cin : Cout, H, W) && dcl_wgrad_dma_supported(nco, nci) ? 1 : 0;
+    return wgrad_plan(N, Cin, Cout, H, W, stride).family != WGRAD_DIRECT ? 1 : 0;
 }
 
 // The weight gradient of conv2d(relu(x * pre_sc[ci] + pre_sh[ci]), w, padding = 1) for the output gradient dy: x is the RAW
@@ -672,17 +541,7 @@ static int wgrad3x3_impl(const float *x, const float *dy, int N, int Cin, int Co
     DCL_CHECK_ARG(Cin > 0 && Cout > 0 && (Cin & 15) == 0 && (Cout & 15) == 0, "channel counts must be multiples of 16");
     DCL_CHECK_ARG((W & 7) == 0, "W must be a multiple of 8");
     DCL_CHECK_ARG(((((uintptr_t)x) | ((uintptr_t)dy)) & 15) == 0, "tensors must be 16-byte aligned");
-    if (stride == 2 && g_s2_native && dcl_wgrad_s2_supported(H, W)) {
-        int nslab = 0;
-        dcl_wgrad_s2_launch(x, dy, N, Cin, Cout, H, W, xamax, xcount, gamax, gcount, part, g_tile_nco, g_tile_nci,
-                            (hipStream_t)stream, &nslab, pre_sc, pre_sh);
-        DCL_LAUNCH_CHECK();
-        const int total = 9 * Cout * Cin;
-        (void)total;
-        launch_wgrad_reduce(part, nslab, Cout, Cin, dw, (hipStream_t)stream);
-        DCL_LAUNCH_CHECK();
-        return 0;
-    }
+    const WgradPlan p = wgrad_plan(N, Cin, Cout, H, W, stride);
     WgradArgs a;
     a.x = x;
     a.dy = dy;
@@ -702,56 +561,44 @@ static int wgrad3x3_impl(const float *x, const float *dy, int N, int Cin, int Co
     a.nseg = 1;
     a.pre_sc = pre_sc;
     a.pre_sh = pre_sh;
-    int nco, nci;
-    bool wm = false;
-    wgrad_plan(N, Cin, Cout, H, W, nco, nci, a.S, a.units,
-               stride == 1 && use_dma(Cin > Cout ? Cin : Cout, H, W) ? &wm : nullptr);
-    a.wave_mode = wm ? g_wave_mode : 0;
-    // adjacent strips for the waves of a workgroup (dcl_wgrad3x3d.hip): LDS-reduced tiles, unclamped split count, strips in fours / pairs
-    a.grp = 1;
-    a.band = (wm && g_wave_band > 0 && H % g_wave_band == 0 && H > g_wave_band) ? g_wave_band : H;
-    if (g_strip_group && !wm && nco * nci <= 4 && a.S == 4 * ((a.S + 3) / 4) && a.S >= 4)
-        a.grp = (a.strips % 4 == 0) ? 4 : ((a.strips % 2 == 0) ? 2 : 1);
-    a.ncig = (Cin / 16 + nci - 1) / nci;
-    a.npairs = (Cout / 16 / nco) * a.ncig;
-    a.nx = (a.S + 3) / 4;                                    // workgroups per pair (4 splits each)
-    dim3 grid((unsigned)(a.npairs * a.nx));      // exactly the populated workgroups, <= 256 whenever pairs <= 256
-    a.rect_i = a.ncig >= 16 ? 16 : (a.ncig >= 8 ? 8 : (a.ncig >= 4 ? 4 : (a.ncig >= 2 ? 2 : 1)));
-    a.rect_c = 32 / a.rect_i;
-    a.rect_mode = a.npairs > 128 ? 1 : 0;
-    if (a.rect_mode) {
-        const int ncog = a.npairs / a.ncig;
-        const int units_r = ((ncog + a.rect_c - 1) / a.rect_c) * ((a.ncig + a.rect_i - 1) / a.rect_i) * a.nx;
-        grid = dim3((unsigned)(((units_r + 7) / 8) * 8 * 32));
-    }
+    a.units = p.units;
+    a.S = p.S;
+    a.ncig = p.ncig;
+    a.npairs = p.npairs;
+    a.nx = p.nx;
+    a.rect_c = p.rect_c;
+    a.rect_i = p.rect_i;
+    a.rect_mode = p.rect_mode;
+    a.wave_mode = p.wave_mode;
+    a.band = p.band;
+    a.grp = p.grp;
+    const dim3 grid(p.grid);
     hipStream_t s = (hipStream_t)stream;
-    if (stride == 1 && use_dma(Cin > Cout ? Cin : Cout, H, W) && dcl_wgrad_dma_supported(nco, nci)) {
-        dcl_wgrad_dma_launch(a, nco, nci, grid, s);
-        DCL_LAUNCH_CHECK();
-        const int total = 9 * Cout * Cin;
-        (void)total;
-        launch_wgrad_reduce(part, (nco * nci <= 4 && !wm) ? a.nx : a.S, Cout, Cin, dw, s);
-        DCL_LAUNCH_CHECK();
-        return 0;
-    }
+    if (p.family == WGRAD_S2 || p.family == WGRAD_S2_DMA) {
+        if (const int rc = dcl_wgrad_s2_launch(a, p, s))
+            return rc;
+    } else if (p.family == WGRAD_DMA) {
+        if (const int rc = dcl_wgrad_dma_launch(a, p.nco, p.nci, grid, s))
+            return rc;
+    } else {
 #define DCL_WG_CASE(o, i)                                                        \
-    if (nco == o && nci == i) {                                                  \
+    if (p.nco == o && p.nci == i) {                                              \
         if (stride == 2)                                                         \
             hipLaunchKernelGGL((k_wgrad3x3<o, i, true>), grid, dim3(256), 0, s, a);  \
         else                                                                     \
             hipLaunchKernelGGL((k_wgrad3x3<o, i, false>), grid, dim3(256), 0, s, a); \
-    }
-    DCL_WG_CASE(2, 2)
-    DCL_WG_CASE(1, 2)
-    DCL_WG_CASE(3, 1)
-    DCL_WG_CASE(2, 1)
-    DCL_WG_CASE(1, 1)
+    } else
+        DCL_WG_CASE(2, 2)
+        DCL_WG_CASE(1, 2)
+        DCL_WG_CASE(3, 1)
+        DCL_WG_CASE(2, 1)
+        DCL_WG_CASE(1, 1)
+        DCL_WGRAD_NO_KERNEL("k_wgrad3x3", p.nco, p.nci);
 #undef DCL_WG_CASE
-    dcl_note_kernel("k_wgrad3x3<%d,%d,%s>", nco, nci, stride == 2 ? "true" : "false");
+        dcl_note_kernel("k_wgrad3x3<%d,%d,%s>", p.nco, p.nci, stride == 2 ? "true" : "false");
+    }
     DCL_LAUNCH_CHECK();
-    const int total = 9 * Cout * Cin;
-    (void)total;
-    launch_wgrad_reduce(part, nco * nci <= 4 ? a.nx : a.S, Cout, Cin, dw, s);
+    launch_wgrad_reduce(part, p.slabs, Cout, Cin, dw, s);
     DCL_LAUNCH_CHECK();
     return 0;
 }

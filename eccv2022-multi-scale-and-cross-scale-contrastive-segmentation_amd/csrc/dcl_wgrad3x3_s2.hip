@@ -20,18 +20,9 @@
 #include <type_traits>
 
 #include "dcl_common.h"
+#include "dcl_wgrad.h"
 
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr float F16_TARGET = 16384.0f;
-
-__device__ __forceinline__ float pow2_scale(float amax)
-{
-    return amax == 0.f ? 1.f : exp2f(fminf(fmaxf(floorf(log2f(F16_TARGET / amax)), -100.f), 100.f));
-}
 
 struct WgradS2Args {
     const float *x, *dy;
@@ -43,22 +34,6 @@ struct WgradS2Args {
     int strips, units, S, ncig, npairs, nx;
     const float *pre_sc, *pre_sh;   // PRE forms: the input operand is relu(x * pre_sc[ci] + pre_sh[ci]) (see k_wgrad3x3d, PRE); else NULL
 };
-
-__device__ __forceinline__ void split2(float v0, float v1, float s, unsigned &hi, unsigned &lo)
-{
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(v0), "v"(s));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(v1), "v"(s));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=&v"(lo) : "v"(v0), "v"(s), "v"(hi));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(v1), "v"(s), "v"(hi));
-}
-
-__device__ __forceinline__ void split1(float v0, float s, unsigned &hi, unsigned &lo)
-{
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(v0), "v"(s));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=&v"(lo) : "v"(v0), "v"(s), "v"(hi));
-}
-
-__device__ __forceinline__ half8 as_half8(u32x4 v) { return __builtin_bit_cast(half8, v); }
 
 // DEEP: operands are loaded two steps ahead of their use instead of one (second set of raw registers)
 // PRE: x is the RAW output of the convolution in front of a training-mode norm, the operand relu(x sc[ci] + sh[ci]) -- the second
@@ -72,64 +47,19 @@ __global__ __launch_bounds__(256, 1) void k_wgrad3x3_s2(WgradS2Args a)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, q4 = lane >> 4, j = lane & 15;
 
     float sx, sg;
-    {
-        float mx = 0.f, mg = 0.f;
-        for (int i = tid; i < a.xcount; i += 256)
-            mx = fmaxf(mx, a.xamax[i]);
-        for (int i = tid; i < a.gcount; i += 256)
-            mg = fmaxf(mg, a.gamax[i]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-            mg = fmaxf(mg, __shfl_xor(mg, o, 64));
-        }
-        if (lane == 0) {
-            wm[wave] = mx;
-            wm[4 + wave] = mg;
-        }
-        __syncthreads();
-        sx = pow2_scale(fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3])));
-        sg = pow2_scale(fmaxf(fmaxf(wm[4], wm[5]), fmaxf(wm[6], wm[7])));
-    }
-    // XCD-aware decode as in k_wgrad3x3: the tile pairs of one pixel split share an XCD (and its L2)
+    wgrad_scales(a, wm, sx, sg);
     int pair, xsplit;
-    {
-        const int nx8 = a.nx & ~7, main_blocks = nx8 * a.npairs;
-        if ((int)blockIdx.x < main_blocks) {
-            const int xcd = blockIdx.x & 7, rest = blockIdx.x >> 3;
-            pair = rest % a.npairs;
-            xsplit = (rest / a.npairs) * 8 + xcd;
-        } else {
-            const int rest = blockIdx.x - main_blocks;
-            pair = rest % a.npairs;
-            xsplit = nx8 + rest / a.npairs;
-        }
-    }
+    wgrad_decode_flat(a, pair, xsplit);         // the tile pairs of one pixel split share an XCD (and its L2)
     const int split = xsplit * 4 + wave;           // a wave past the last split gets an empty run and adds zeros
     const int cog = pair / a.ncig, cig = pair - cog * a.ncig;
     const int co0 = cog * NCO * 16, ci0 = cig * NCI * 16;
     const size_t plane = (size_t)a.H * a.W, dplane = (size_t)a.Hd * a.Wd;
     bool ci_ok[NCI];
-#pragma unroll
-    for (int u = 0; u < NCI; ++u)
-        ci_ok[u] = ci0 + 16 * u < a.Cin;
-    float psc[NCI], psh[NCI];               // PRE: the norm's map of this lane's channel of ci tile u
-#pragma unroll
-    for (int u = 0; u < NCI; ++u) {
-        const int ch = ci_ok[u] ? ci0 + 16 * u + j : ci0 + j;
-        psc[u] = PRE ? a.pre_sc[ch] : 1.f;
-        psh[u] = PRE ? a.pre_sh[ch] : 0.f;
-    }
-    auto pre = [&](float v, int u) { return PRE ? fmaxf(__builtin_fmaf(v, psc[u], psh[u]), 0.f) : v; };
+    wgrad_ci_ok(ci_ok, ci0, a.Cin);
+    const WgradPreMap<NCI, PRE> pre(a.pre_sc, a.pre_sh, ci_ok, ci0, j);
 
     f32x4 acc[NCO][NCI][9];
-#pragma unroll
-    for (int t = 0; t < NCO; ++t)
-#pragma unroll
-        for (int u = 0; u < NCI; ++u)
-#pragma unroll
-            for (int k = 0; k < 9; ++k)
-                acc[t][u][k] = f32x4{0.f, 0.f, 0.f, 0.f};
+    DCL_WGRAD_CLEAR(acc, 9);
 
     const long long T = (long long)a.units * a.Hd;             // units = images x strips of 32 output pixels
     long long t = min(T, T * split / a.S);
@@ -283,59 +213,9 @@ __global__ __launch_bounds__(256, 1) void k_wgrad3x3_s2(WgradS2Args a)
             step(std::integral_constant<int, 0>{}, yo);
     }
 
-    // (w0 + w1) + (w2 + w3) through LDS, one slab per workgroup
-    {
-        constexpr int NREG = NCO * NCI * 36;
-        __shared__ float red[2][NREG][64];
-        auto put = [&](int b) {
-#pragma unroll
-            for (int t2 = 0; t2 < NCO; ++t2)
-#pragma unroll
-                for (int u = 0; u < NCI; ++u)
-#pragma unroll
-                    for (int k = 0; k < 9; ++k)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            red[b][((t2 * NCI + u) * 9 + k) * 4 + q][lane] = acc[t2][u][k][q];
-        };
-        auto add = [&](int b) {
-#pragma unroll
-            for (int t2 = 0; t2 < NCO; ++t2)
-#pragma unroll
-                for (int u = 0; u < NCI; ++u)
-#pragma unroll
-                    for (int k = 0; k < 9; ++k)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            acc[t2][u][k][q] += red[b][((t2 * NCI + u) * 9 + k) * 4 + q][lane];
-        };
-        if (wave & 1)
-            put(wave >> 1);
-        __syncthreads();
-        if (!(wave & 1))
-            add(wave >> 1);
-        __syncthreads();
-        if (wave == 2)
-            put(0);
-        __syncthreads();
-        if (wave != 0)
-            return;
-        add(0);
-    }
-    const float inv = 1.0f / (sx * sg);
-    float *out = a.part + (size_t)xsplit * 9 * a.Cout * a.Cin;
-#pragma unroll
-    for (int t2 = 0; t2 < NCO; ++t2)
-#pragma unroll
-        for (int u = 0; u < NCI; ++u)
-#pragma unroll
-            for (int k = 0; k < 9; ++k)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int co = co0 + 16 * t2 + 4 * q4 + q, ci = ci0 + 16 * u + j;
-                    if (ci_ok[u])
-                        out[((size_t)k * a.Cout + co) * a.Cin + ci] = acc[t2][u][k][q] * inv;
-                }
+    // one slab per workgroup: [xsplit][tap][co][ci]
+    __shared__ float red[2][NCO * NCI * 36][64];
+    wgrad_reduce_store(acc, red, wave, lane, a.part, xsplit, a.Cout, a.Cin, co0, ci0, ci_ok, q4, j, sx, sg);
 }
 
 // ---- LDS-DMA form (round 5): the x rows -- ten of the sixteen vector-memory instructions of a step above, each one touching 64
@@ -346,27 +226,6 @@ __global__ __launch_bounds__(256, 1) void k_wgrad3x3_s2(WgradS2Args a)
 // ds_read_b128 pass fall into 16 different bank groups) and is read back in MFMA order one to two steps later.  The dY rows (six
 // instructions per step) stay on direct loads.  Same arithmetic, order of accumulation and slabs as k_wgrad3x3_s2: bitwise the same
 // result.
-__device__ __forceinline__ const float *uniform_ptr(const float *p)
-{
-    const unsigned long long v = (unsigned long long)(uintptr_t)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (const float *)(uintptr_t)(((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ void dma16(const void *gbase, unsigned voff, unsigned lds_dst)
-{
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(gbase), "s"(lds_dst)
-                 : "memory");
-}
-template <int N>
-__device__ __forceinline__ void vm_wait()
-{
-    static_assert(N >= 0 && N < 64, "vmcnt immediate");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 constexpr int S2_BP = 17;                                 // pieces per staged x row: left-halo piece + 16 pieces of 4 pixels
 
 template <int NCO, int NCI, bool PRE = false>
@@ -386,54 +245,16 @@ __global__ __launch_bounds__(256, 1) void k_wgrad3x3_s2d(WgradS2Args a)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, q4 = lane >> 4, j = lane & 15;
 
     float sx, sg;
-    {
-        float mx = 0.f, mg = 0.f;
-        for (int i = tid; i < a.xcount; i += 256)
-            mx = fmaxf(mx, a.xamax[i]);
-        for (int i = tid; i < a.gcount; i += 256)
-            mg = fmaxf(mg, a.gamax[i]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-            mg = fmaxf(mg, __shfl_xor(mg, o, 64));
-        }
-        if (lane == 0) {
-            wm[wave] = mx;
-            wm[4 + wave] = mg;
-        }
-        __syncthreads();
-        sx = pow2_scale(fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3])));
-        sg = pow2_scale(fmaxf(fmaxf(wm[4], wm[5]), fmaxf(wm[6], wm[7])));
-    }
+    wgrad_scales(a, wm, sx, sg);
     int pair, xsplit;
-    {
-        const int nx8 = a.nx & ~7, main_blocks = nx8 * a.npairs;
-        if ((int)blockIdx.x < main_blocks) {
-            const int xcd = blockIdx.x & 7, rest = blockIdx.x >> 3;
-            pair = rest % a.npairs;
-            xsplit = (rest / a.npairs) * 8 + xcd;
-        } else {
-            const int rest = blockIdx.x - main_blocks;
-            pair = rest % a.npairs;
-            xsplit = nx8 + rest / a.npairs;
-        }
-    }
+    wgrad_decode_flat(a, pair, xsplit);         // the tile pairs of one pixel split share an XCD (and its L2)
     const int split = xsplit * 4 + wave;
     const int cog = pair / a.ncig, cig = pair - cog * a.ncig;
     const int co0 = cog * NCO * 16, ci0 = cig * NCI * 16;
     const size_t plane = (size_t)a.H * a.W, dplane = (size_t)a.Hd * a.Wd;
     bool ci_ok[NCI];
-#pragma unroll
-    for (int u = 0; u < NCI; ++u)
-        ci_ok[u] = ci0 + 16 * u < a.Cin;
-    float psc[NCI], psh[NCI];               // PRE: the norm's map of this lane's channel of ci tile u
-#pragma unroll
-    for (int u = 0; u < NCI; ++u) {
-        const int ch = ci_ok[u] ? ci0 + 16 * u + j : ci0 + j;
-        psc[u] = PRE ? a.pre_sc[ch] : 1.f;
-        psh[u] = PRE ? a.pre_sh[ch] : 0.f;
-    }
-    auto pre = [&](float v, int u) { return PRE ? fmaxf(__builtin_fmaf(v, psc[u], psh[u]), 0.f) : v; };
+    wgrad_ci_ok(ci_ok, ci0, a.Cin);
+    const WgradPreMap<NCI, PRE> pre(a.pre_sc, a.pre_sh, ci_ok, ci0, j);
 
     // DMA geometry of this lane, per instruction m of a row set: piece P = 64 m + lane in [row][piece] order (the tail repeats piece 0)
     unsigned chanB[NIR];
@@ -455,13 +276,7 @@ __global__ __launch_bounds__(256, 1) void k_wgrad3x3_s2d(WgradS2Args a)
     const unsigned brdo = (unsigned)((j * S2_BP + 1 + 4 * q4) * 16);      // lane (q4, j): row j, the 16 pixels at 2 (px0 + 8 q4)
 
     f32x4 acc[NCO][NCI][9];
-#pragma unroll
-    for (int t = 0; t < NCO; ++t)
-#pragma unroll
-        for (int u = 0; u < NCI; ++u)
-#pragma unroll
-            for (int k = 0; k < 9; ++k)
-                acc[t][u][k] = f32x4{0.f, 0.f, 0.f, 0.f};
+    DCL_WGRAD_CLEAR(acc, 9);
 
     const long long T = (long long)a.units * a.Hd;
     long long t = min(T, T * split / a.S);
@@ -671,45 +486,11 @@ __global__ __launch_bounds__(256, 1) void k_wgrad3x3_s2d(WgradS2Args a)
     }
     vm_wait<0>();
 
-    // (w0 + w1) + (w2 + w3) through LDS (the staging rings are done: their memory is reused), one slab per workgroup
-    {
-        __syncthreads();
-        float(*red)[NREG][64] = (float(*)[NREG][64])smem;
-        auto put = [&](int b) {
-#pragma unroll
-            for (int t2 = 0; t2 < NCO; ++t2)
-#pragma unroll
-                for (int u = 0; u < NCI; ++u)
-#pragma unroll
-                    for (int k = 0; k < 9; ++k)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            red[b][((t2 * NCI + u) * 9 + k) * 4 + q][lane] = acc[t2][u][k][q];
-        };
-        auto add = [&](int b) {
-#pragma unroll
-            for (int t2 = 0; t2 < NCO; ++t2)
-#pragma unroll
-                for (int u = 0; u < NCI; ++u)
-#pragma unroll
-                    for (int k = 0; k < 9; ++k)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            acc[t2][u][k][q] += red[b][((t2 * NCI + u) * 9 + k) * 4 + q][lane];
-        };
-        if (wave & 1)
-            put(wave >> 1);
-        __syncthreads();
-        if (!(wave & 1))
-            add(wave >> 1);
-        __syncthreads();
-        if (wave == 2)
-            put(0);
-        __syncthreads();
-        if (wave != 0)
-            return;
-        add(0);
-    }
+    __syncthreads();                            // the staging rings are done: their memory is reused for the reduction
+    if (!wgrad_combine(acc, (float(*)[NREG][64])smem, wave, lane))
+        return;
+    // (the store of wgrad_store_slab, kept in place: through the shared function this kernel alone compiles to 4 more VGPRs and
+    // a different pairing of the combine's LDS reads)
     const float inv = 1.0f / (sx * sg);
     float *out = a.part + (size_t)xsplit * 9 * a.Cout * a.Cin;
 #pragma unroll
@@ -726,14 +507,16 @@ __global__ __launch_bounds__(256, 1) void k_wgrad3x3_s2d(WgradS2Args a)
                 }
 }
 
-struct S2Plan {
-    int nco, nci, ncig, npairs, units, S, nx;
-};
+}  // namespace
 
-S2Plan s2_plan(int N, int Cin, int Cout, int H, int W, int force_nco, int force_nci)
+bool dcl_wgrad_s2_supported(int H, int W) { return W % 16 == 0 && H >= 1; }
+
+static bool g_s2_dma = true;
+void dcl_wgrad_s2_set_dma(int on) { g_s2_dma = on != 0; }
+
+void dcl_wgrad_s2_plan(int N, int Cin, int Cout, int H, int W, int force_nco, int force_nci, WgradPlan &p)
 {
     const int cot = Cout / 16, cit = Cin / 16, Hd = (H - 1) / 2 + 1, Wd = W / 2;
-    S2Plan p;
     // four tiles per wave at most (LDS reduction across the waves, registers); threes when the co tiles allow it
     p.nco = (cot % 3 == 0) ? 3 : (cot % 2 == 0) ? 2 : 1;
     p.nci = 1;
@@ -755,68 +538,57 @@ S2Plan s2_plan(int N, int Cin, int Cout, int H, int W, int force_nco, int force_
     if ((long long)p.S > (long long)p.units * Hd)
         p.S = p.units * Hd;
     p.nx = (p.S + 3) / 4;
-    return p;
-}
-
-}  // namespace
-
-bool dcl_wgrad_s2_supported(int H, int W) { return W % 16 == 0 && H >= 1; }
-
-static bool g_s2_dma = true;
-void dcl_wgrad_s2_set_dma(int on) { g_s2_dma = on != 0; }
-
-int dcl_wgrad_s2_slabs(int N, int Cin, int Cout, int H, int W, int force_nco, int force_nci)
-{
-    return s2_plan(N, Cin, Cout, H, W, force_nco, force_nci).nx;
-}
-
-// kernel only; the caller sums the *nslab slabs (k_wgrad_reduce)
-void dcl_wgrad_s2_launch(const float *x, const float *dy, int N, int Cin, int Cout, int H, int W, const float *xamax,
-                         int xcount, const float *gamax, int gcount, float *part, int force_nco, int force_nci,
-                         hipStream_t s, int *nslab, const float *pre_sc, const float *pre_sh)
-{
-    const S2Plan p = s2_plan(N, Cin, Cout, H, W, force_nco, force_nci);
-    WgradS2Args a;
-    a.pre_sc = pre_sc;
-    a.pre_sh = pre_sh;
-    a.x = x; a.dy = dy; a.part = part; a.xamax = xamax; a.gamax = gamax; a.xcount = xcount; a.gcount = gcount;
-    a.N = N; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
-    a.Hd = (H - 1) / 2 + 1;
-    a.Wd = W / 2;
-    a.strips = (a.Wd + 31) / 32;
-    a.units = p.units; a.S = p.S; a.ncig = p.ncig; a.npairs = p.npairs; a.nx = p.nx;
-    *nslab = p.nx;
-    const dim3 grid((unsigned)(p.npairs * p.nx));
+    p.grid = (unsigned)(p.npairs * p.nx);
+    p.slabs = p.nx;
     // LDS-DMA staging of the x rows (k_wgrad3x3_s2d) unless switched off (dcl_wgrad3x3_set_variant(0)) or the rows are too far
     // apart for the 32-bit lane offsets
     // (one ci tile per wave only: with two, three ring slots of four waves do not fit the 160 KB of LDS)
-    if (g_s2_dma && p.nci == 1 && (size_t)Cin * H * W * 4 < ((size_t)1 << 32)) {
+    p.family = g_s2_dma && p.nci == 1 && (size_t)Cin * H * W * 4 < ((size_t)1 << 32) ? WGRAD_S2_DMA : WGRAD_S2;
+}
+
+int dcl_wgrad_s2_launch(const WgradArgs &w, const WgradPlan &p, hipStream_t s)
+{
+    WgradS2Args a;
+    a.pre_sc = w.pre_sc;
+    a.pre_sh = w.pre_sh;
+    a.x = w.x; a.dy = w.dy; a.part = w.part; a.xamax = w.xamax; a.gamax = w.gamax; a.xcount = w.xcount; a.gcount = w.gcount;
+    a.N = w.N; a.Cin = w.Cin; a.Cout = w.Cout; a.H = w.H; a.W = w.W;
+    a.Hd = (w.H - 1) / 2 + 1;
+    a.Wd = w.W / 2;
+    a.strips = (a.Wd + 31) / 32;
+    a.units = p.units; a.S = p.S; a.ncig = p.ncig; a.npairs = p.npairs; a.nx = p.nx;
+    const dim3 grid(p.grid);
+    const bool pre = w.pre_sc != nullptr;
+    if (p.family == WGRAD_S2_DMA) {
 #define DCL_S2D_CASE(o, i)                                                      \
     if (p.nco == o && p.nci == i) {                                             \
-        if (pre_sc)                                                             \
+        if (pre)                                                                \
             hipLaunchKernelGGL((k_wgrad3x3_s2d<o, i, true>), grid, dim3(256), 0, s, a);  \
         else                                                                    \
             hipLaunchKernelGGL((k_wgrad3x3_s2d<o, i>), grid, dim3(256), 0, s, a);        \
-    }
+    } else
         DCL_S2D_CASE(3, 1)
         DCL_S2D_CASE(2, 1)
         DCL_S2D_CASE(1, 1)
+        DCL_WGRAD_NO_KERNEL("k_wgrad3x3_s2d", p.nco, p.nci);
 #undef DCL_S2D_CASE
-        dcl_note_kernel(pre_sc ? "k_wgrad3x3_s2d_pre<%d,%d>" : "k_wgrad3x3_s2d<%d,%d>", p.nco, p.nci);
-        return;
+        dcl_note_kernel(pre ? "k_wgrad3x3_s2d_pre<%d,%d>" : "k_wgrad3x3_s2d<%d,%d>", p.nco, p.nci);
+        return 0;
     }
 #define DCL_S2_CASE(o, i, deep)                                                 \
     if (p.nco == o && p.nci == i) {                                             \
-        if (pre_sc)                                                             \
+        if (pre)                                                                \
             hipLaunchKernelGGL((k_wgrad3x3_s2<o, i, deep, true>), grid, dim3(256), 0, s, a);  \
         else                                                                    \
             hipLaunchKernelGGL((k_wgrad3x3_s2<o, i, deep>), grid, dim3(256), 0, s, a);        \
-    }
+    } else
     DCL_S2_CASE(3, 1, true)
     DCL_S2_CASE(2, 2, false)
     DCL_S2_CASE(2, 1, true)
     DCL_S2_CASE(1, 2, true)
     DCL_S2_CASE(1, 1, true)
+    DCL_WGRAD_NO_KERNEL("k_wgrad3x3_s2", p.nco, p.nci);
 #undef DCL_S2_CASE
-    dcl_note_kernel(pre_sc ? "k_wgrad3x3_s2_pre<%d,%d>" : "k_wgrad3x3_s2<%d,%d>", p.nco, p.nci);
+    dcl_note_kernel(pre ? "k_wgrad3x3_s2_pre<%d,%d>" : "k_wgrad3x3_s2<%d,%d>", p.nco, p.nci);
+    return 0;
 }

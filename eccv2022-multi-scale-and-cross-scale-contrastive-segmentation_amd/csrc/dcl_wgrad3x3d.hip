@@ -19,67 +19,10 @@
 #include "dcl_common.h"
 #include "dcl_wgrad.h"
 
-// Bound probes (tools/probes/conv_bounds.sh; 0 in the product): 1 = no MFMAs, 2 = no LDS-DMA.  Results are wrong.
-#ifndef DCL_WG_PROBE
-#define DCL_WG_PROBE 0
-#endif
+// Bound probes (DCL_WG_PROBE, dcl_f16x3.h): bit 1 = no MFMAs
 #define DCL_WMFMA(A, B, C) ((DCL_WG_PROBE & 1) ? (C) : __builtin_amdgcn_mfma_f32_16x16x32_f16((A), (B), (C), 0, 0, 0))
 
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr float F16_TARGET = 16384.0f;
-
-__device__ __forceinline__ float pow2_scale(float amax)
-{
-    return amax == 0.f ? 1.f : exp2f(fminf(fmaxf(floorf(log2f(F16_TARGET / amax)), -100.f), 100.f));
-}
-
-__device__ __forceinline__ void split2(float v0, float v1, float s, unsigned &hi, unsigned &lo)
-{
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(v0), "v"(s));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(v1), "v"(s));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=&v"(lo) : "v"(v0), "v"(s), "v"(hi));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(v1), "v"(s), "v"(hi));
-}
-
-__device__ __forceinline__ void split1(float v0, float s, unsigned &hi, unsigned &lo)
-{
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(v0), "v"(s));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=&v"(lo) : "v"(v0), "v"(s), "v"(hi));
-}
-
-__device__ __forceinline__ half8 as_half8(u32x4 v) { return __builtin_bit_cast(half8, v); }
-
-// one LDS-DMA wave instruction: lane i copies the 16 bytes at gbase + voff(i) to LDS byte address lds_dst + 16 i.
-// (inline asm: the compiler puts s_waitcnt vmcnt(0) in front of every LDS read that follows the builtin.)
-__device__ __forceinline__ const float *uniform_ptr(const float *p)
-{
-    const unsigned long long v = (unsigned long long)(uintptr_t)p;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (const float *)(uintptr_t)(((unsigned long long)hi << 32) | lo);
-}
-
-// gbase and lds_dst must be wave-uniform (scalar registers)
-__device__ __forceinline__ void dma16(const void *gbase, unsigned voff, unsigned lds_dst)
-{
-    if (DCL_WG_PROBE & 2)
-        return;
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(gbase), "s"(lds_dst)
-                 : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void dma_wait()
-{
-    static_assert(N >= 0 && N < 64, "vmcnt immediate");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 constexpr int APIECES = 9, BPIECES = 11;          // 16-byte pieces per staged row: 8 (+ 2 halo) + 1 pad
 #ifndef DCL_WG_SPREAD
@@ -106,9 +49,9 @@ __global__ __launch_bounds__(256, 1) void k_wgrad3x3d(WgradArgs a)
     constexpr int NIA = (NCO * 16 * APIECES + 63) / 64, NIB = (NCI * 16 * BPIECES + 63) / 64, NI = NIA + NIB;
     constexpr int NS = 3;                                   // ring slots: rows are fetched two steps ahead
     constexpr int SLOTB = NI * 1024, STAGEB = 4 * NS * SLOTB;
-    constexpr bool LDSRED = !WAVE && NCO * NCI <= 4;
+    static_assert(NCO * NCI <= 4, "four tiles per wave at most (six spilled in the main loop)");
     constexpr int NREG = NCO * NCI * 36;
-    constexpr int REDB = LDSRED ? 2 * NREG * 64 * 4 : 0;
+    constexpr int REDB = WAVE ? 0 : 2 * NREG * 64 * 4;
     constexpr int SMEMB = STAGEB > REDB ? STAGEB : REDB;
     static_assert(SMEMB + 64 <= 160 * 1024, "LDS");
     __shared__ __attribute__((aligned(1024))) unsigned char smem[SMEMB];
@@ -120,79 +63,25 @@ __global__ __launch_bounds__(256, 1) void k_wgrad3x3d(WgradArgs a)
     float sx = 0.f, sg = 0.f;
     bool have_scales = false;
     auto scales = [&]() {
-        float mx = 0.f, mg = 0.f;
-        for (int i = tid; i < a.xcount; i += 256)
-            mx = fmaxf(mx, a.xamax[i]);
-        for (int i = tid; i < a.gcount; i += 256)
-            mg = fmaxf(mg, a.gamax[i]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-            mg = fmaxf(mg, __shfl_xor(mg, o, 64));
-        }
-        if (lane == 0) {
-            wm[wave] = mx;
-            wm[4 + wave] = mg;
-        }
-        __syncthreads();
-        sx = pow2_scale(fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3])));
-        sg = pow2_scale(fmaxf(fmaxf(wm[4], wm[5]), fmaxf(wm[6], wm[7])));
+        wgrad_scales(a, wm, sx, sg);
         have_scales = true;
     };
     // workgroup -> (tile pair, pixel split): as k_wgrad3x3
     int pair, xsplit, wsplit = 0;
-    if (WAVE) {
-        const int xcd = blockIdx.x & 7, base = a.npairs >> 3, rem = a.npairs & 7;
-        const int mine = base + (xcd < rem ? 1 : 0), first = xcd * base + min(xcd, rem);
-        const int job = (int)(blockIdx.x >> 3) * 4 + wave;
-        const int pl = a.wave_mode == 2 ? job % mine : job / a.S, sp = a.wave_mode == 2 ? job / mine : job - pl * a.S;
-        xsplit = 0;
-        if (a.wave_mode == 2 ? sp < a.S : pl < mine) {
-            pair = first + pl;
-            wsplit = sp;
-        } else {                                // no job for this wave: an empty run of pair 0 (it still meets the barrier)
-            pair = 0;
-            wsplit = a.S;
-        }
-    } else if (a.rect_mode) {
-        const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-        const int unit = (slot >> 5) * 8 + xcd, idx = slot & 31;
-        const int ncog = a.npairs / a.ncig, rects_i = (a.ncig + a.rect_i - 1) / a.rect_i;
-        const int nrect = ((ncog + a.rect_c - 1) / a.rect_c) * rects_i;
-        const int rect = unit % nrect;
-        xsplit = unit / nrect;
-        const int cg = (rect / rects_i) * a.rect_c + idx / a.rect_i, ci = (rect % rects_i) * a.rect_i + idx % a.rect_i;
-        if (xsplit >= a.nx || cg >= ncog || ci >= a.ncig)
+    if (WAVE)
+        wgrad_decode_wave(a, wave, pair, xsplit, wsplit);
+    else if (a.rect_mode) {
+        if (!wgrad_decode_rect(a, pair, xsplit))
             return;
-        pair = cg * a.ncig + ci;
-    } else {
-        const int nx8 = a.nx & ~7, main_blocks = nx8 * a.npairs;
-        if ((int)blockIdx.x < main_blocks) {
-            const int xcd = blockIdx.x & 7, rest = blockIdx.x >> 3;
-            pair = rest % a.npairs;
-            xsplit = (rest / a.npairs) * 8 + xcd;
-        } else {
-            const int rest = blockIdx.x - main_blocks;
-            pair = rest % a.npairs;
-            xsplit = nx8 + rest / a.npairs;
-        }
-    }
+    } else
+        wgrad_decode_flat(a, pair, xsplit);
     const int split = WAVE ? wsplit : xsplit * 4 + wave;
     const int cog = pair / a.ncig, cig = pair - cog * a.ncig;
     const int co0 = cog * NCO * 16, ci0 = cig * NCI * 16;
     const size_t plane = (size_t)a.H * a.W;
     bool ci_ok[NCI];
-#pragma unroll
-    for (int u = 0; u < NCI; ++u)
-        ci_ok[u] = ci0 + 16 * u < a.Cin;
-    float psc[NCI], psh[NCI];               // PRE: the norm's map of this lane's channel of ci tile u
-#pragma unroll
-    for (int u = 0; u < NCI; ++u) {
-        const int ch = ci_ok[u] ? ci0 + 16 * u + j : ci0 + j;
-        psc[u] = PRE ? a.pre_sc[ch] : 1.f;
-        psh[u] = PRE ? a.pre_sh[ch] : 0.f;
-    }
-    auto pre = [&](float v, int u) { return PRE ? fmaxf(__builtin_fmaf(v, psc[u], psh[u]), 0.f) : v; };
+    wgrad_ci_ok(ci_ok, ci0, a.Cin);
+    const WgradPreMap<NCI, PRE> pre(a.pre_sc, a.pre_sh, ci_ok, ci0, j);
 
     // staging geometry of this lane, per DMA instruction m: which (tile, row, piece) of the slot image it carries
     // (piece = 64 m + lane in [tile][row][piece] order; the tail of the last instruction repeats piece 0)
@@ -226,13 +115,7 @@ __global__ __launch_bounds__(256, 1) void k_wgrad3x3d(WgradArgs a)
     const unsigned brdo = (unsigned)(NIA * 1024 + (j * BPIECES + 1 + 2 * q4) * 16);
 
     f32x4 acc[NCO][NCI][9];
-#pragma unroll
-    for (int t = 0; t < NCO; ++t)
-#pragma unroll
-        for (int u = 0; u < NCI; ++u)
-#pragma unroll
-            for (int k = 0; k < 9; ++k)
-                acc[t][u][k] = f32x4{0.f, 0.f, 0.f, 0.f};
+    DCL_WGRAD_CLEAR(acc, 9);
 
     // Which rows: split `split` of S over the columns (image, strip) x H rows -- or, a.grp = G > 1 (workgroup form only), the G
     // waves w % G of a workgroup take G ADJACENT strips over the SAME rows (sub-range w / G of the workgroup's share of the
@@ -357,7 +240,7 @@ __global__ __launch_bounds__(256, 1) void k_wgrad3x3d(WgradArgs a)
         //   group r + 3 is issued into slot i % 3 (group r's, read one step ago),
         //   MFMAs of tap rows ky = 1, 0.
         half8 A[3][NCO][2], B[2][3][NCI][2];
-        dma_wait<0>();                          // nothing of the previous column is still landing in the ring
+        vm_wait<0>();                          // nothing of the previous column is still landing in the ring
         dma_group(r0 - 2, 0);
         dma_group(r0 - 1, 1);
         dma_group(r0, 2);
@@ -366,7 +249,7 @@ __global__ __launch_bounds__(256, 1) void k_wgrad3x3d(WgradArgs a)
         sx_c = oct_ok ? sx : 0.f;
         sx_l = (oct_ok && px > 0) ? sx : 0.f;
         sx_r = (px + 8 < a.W) ? sx : 0.f;
-        dma_wait<0>();
+        vm_wait<0>();
         {
             f32x4 ra[NCO][2], rb[NCI][2];
             float rl[NCI], rr[NCI];
@@ -404,7 +287,7 @@ __global__ __launch_bounds__(256, 1) void k_wgrad3x3d(WgradArgs a)
             using BS = std::integral_constant<int, ph % 2>;
             f32x4 ra[NCO][2], rb[NCI][2];
             float rl[NCI], rr[NCI];
-            dma_wait<NI>();                                            // group r + 1 is in LDS (group r + 2 may be landing)
+            vm_wait<NI>();                                            // group r + 1 is in LDS (group r + 2 may be landing)
             read_A((ph + 1) % 3, ra);
             read_B((ph + 1) % 3, rb, rl, rr);
             mfma_row(I{}, BS{}, std::integral_constant<int, 2>{});
@@ -468,61 +351,15 @@ __global__ __launch_bounds__(256, 1) void k_wgrad3x3d(WgradArgs a)
         if (r + 4 < r1)
             step(std::integral_constant<int, 4>{}, r + 4);
     }
-    dma_wait<0>();
+    vm_wait<0>();
 
-    if (LDSRED) {
-        __syncthreads();                        // every wave is done with its staging ring: reuse it for the reduction
-        float(*red)[NREG][64] = (float(*)[NREG][64])smem;
-        auto put = [&](int b) {
-#pragma unroll
-            for (int t2 = 0; t2 < NCO; ++t2)
-#pragma unroll
-                for (int u = 0; u < NCI; ++u)
-#pragma unroll
-                    for (int k = 0; k < 9; ++k)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            red[b][((t2 * NCI + u) * 9 + k) * 4 + q][lane] = acc[t2][u][k][q];
-        };
-        auto add = [&](int b) {
-#pragma unroll
-            for (int t2 = 0; t2 < NCO; ++t2)
-#pragma unroll
-                for (int u = 0; u < NCI; ++u)
-#pragma unroll
-                    for (int k = 0; k < 9; ++k)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            acc[t2][u][k][q] += red[b][((t2 * NCI + u) * 9 + k) * 4 + q][lane];
-        };
-        if (wave & 1)
-            put(wave >> 1);
-        __syncthreads();
-        if (!(wave & 1))
-            add(wave >> 1);
-        __syncthreads();
-        if (wave == 2)
-            put(0);
-        __syncthreads();
-        if (wave != 0)
-            return;
-        add(0);
-    } else if (split >= a.S)
+    if (WAVE) {                                 // one slab per wave: the four waves of a workgroup belong to different pairs
+        if (split < a.S)
+            wgrad_store_slab(acc, a.part, split, a.Cout, a.Cin, co0, ci0, ci_ok, q4, j, sx, sg);
         return;
-    const float inv = 1.0f / (sx * sg);
-    float *out = a.part + (size_t)(LDSRED ? xsplit : split) * 9 * a.Cout * a.Cin;
-#pragma unroll
-    for (int t2 = 0; t2 < NCO; ++t2)
-#pragma unroll
-        for (int u = 0; u < NCI; ++u)
-#pragma unroll
-            for (int k = 0; k < 9; ++k)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int co = co0 + 16 * t2 + 4 * q4 + q, ci = ci0 + 16 * u + j;
-                    if (ci_ok[u])
-                        out[((size_t)k * a.Cout + co) * a.Cin + ci] = acc[t2][u][k][q] * inv;
-                }
+    }
+    __syncthreads();                            // every wave is done with its staging ring: reuse it for the reduction
+    wgrad_reduce_store(acc, (float(*)[NREG][64])smem, wave, lane, a.part, xsplit, a.Cout, a.Cin, co0, ci0, ci_ok, q4, j, sx, sg);
 }
 
 
@@ -560,38 +397,11 @@ __global__ __launch_bounds__(256, 1) void k_wgrad1x1d(Wgrad1Args a)
     float sx = 0.f, sg = 0.f;
     bool have_scales = false;
     auto scales = [&]() {
-        float mx = 0.f, mg = 0.f;
-        for (int i = tid; i < a.xcount; i += 256)
-            mx = fmaxf(mx, a.xamax[i]);
-        for (int i = tid; i < a.gcount; i += 256)
-            mg = fmaxf(mg, a.gamax[i]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-            mg = fmaxf(mg, __shfl_xor(mg, o, 64));
-        }
-        if (lane == 0) {
-            wm[wave] = mx;
-            wm[4 + wave] = mg;
-        }
-        __syncthreads();
-        sx = pow2_scale(fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3])));
-        sg = pow2_scale(fmaxf(fmaxf(wm[4], wm[5]), fmaxf(wm[6], wm[7])));
+        wgrad_scales(a, wm, sx, sg);
         have_scales = true;
     };
     int pair, xsplit;
-    {
-        const int nx8 = a.nx & ~7, main_blocks = nx8 * a.npairs;
-        if ((int)blockIdx.x < main_blocks) {
-            const int xcd = blockIdx.x & 7, rest = blockIdx.x >> 3;
-            pair = rest % a.npairs;
-            xsplit = (rest / a.npairs) * 8 + xcd;
-        } else {
-            const int rest = blockIdx.x - main_blocks;
-            pair = rest % a.npairs;
-            xsplit = nx8 + rest / a.npairs;
-        }
-    }
+    wgrad_decode_flat(a, pair, xsplit);
     const int split = xsplit * 4 + wave;
     const int cog = pair / a.ncig, cig = pair - cog * a.ncig;
     const int co0 = cog * NCO * 16, ci0 = cig * NCI * 16;
@@ -623,12 +433,8 @@ __global__ __launch_bounds__(256, 1) void k_wgrad1x1d(Wgrad1Args a)
     const unsigned ardo = (unsigned)(j * APIECES + 2 * q4) * 16;
     const unsigned brdo = (unsigned)(NIA * 1024) + ardo;
 
-    f32x4 acc[NCO][NCI];
-#pragma unroll
-    for (int t = 0; t < NCO; ++t)
-#pragma unroll
-        for (int u = 0; u < NCI; ++u)
-            acc[t][u] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 acc[NCO][NCI][1];
+    DCL_WGRAD_CLEAR(acc, 1);
 
     const long long T = (long long)a.units * a.H;
     long long t = min(T, T * split / a.S);
@@ -689,7 +495,7 @@ __global__ __launch_bounds__(256, 1) void k_wgrad1x1d(Wgrad1Args a)
         };
 
         half8 FA[2][NCO][2], FB[2][NCI][2];
-        dma_wait<0>();
+        vm_wait<0>();
 #pragma unroll
         for (int g = 0; g <= D; ++g)
             dma_group(r0 + g, g);
@@ -697,7 +503,7 @@ __global__ __launch_bounds__(256, 1) void k_wgrad1x1d(Wgrad1Args a)
             scales();
         sx_c = oct_ok ? sx : 0.f;
         sg_c = oct_ok ? sg : 0.f;
-        dma_wait<D * NI>();
+        vm_wait<D * NI>();
         {
             f32x4 ra[NCO][2], rb[NCI][2];
             read_rows(0, ra, rb);
@@ -713,7 +519,7 @@ __global__ __launch_bounds__(256, 1) void k_wgrad1x1d(Wgrad1Args a)
         auto step = [&](auto PH, int r) {
             constexpr int ph = decltype(PH)::value, fs = ph % 2;
             f32x4 ra[NCO][2], rb[NCI][2];
-            dma_wait<(D - 1) * NI>();
+            vm_wait<(D - 1) * NI>();
             read_rows((ph + 1) % NS, ra, rb);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         // slot ph % NS was read a step ago; this one now
             dma_group(r + NS, ph % NS);
@@ -723,8 +529,7 @@ __global__ __launch_bounds__(256, 1) void k_wgrad1x1d(Wgrad1Args a)
                 for (int t2 = 0; t2 < NCO; ++t2)
 #pragma unroll
                     for (int u = 0; u < NCI; ++u)
-                        acc[t2][u] = DCL_WMFMA(FA[fs][t2][pass == 2 ? 1 : 0],
-                                                                            FB[fs][u][pass == 1 ? 1 : 0], acc[t2][u]);
+                        acc[t2][u][0] = DCL_WMFMA(FA[fs][t2][pass == 2 ? 1 : 0], FB[fs][u][pass == 1 ? 1 : 0], acc[t2][u][0]);
 #pragma unroll
             for (int t2 = 0; t2 < NCO; ++t2)
                 cvt8(ra[t2], sg_c, FA[fs ^ 1][t2]);
@@ -752,50 +557,13 @@ __global__ __launch_bounds__(256, 1) void k_wgrad1x1d(Wgrad1Args a)
         if (r + 4 < r1)
             step(std::integral_constant<int, 4>{}, r + 4);
     }
-    dma_wait<0>();
-    __syncthreads();
-    {
-        float(*red)[NREG][64] = (float(*)[NREG][64])smem;
-        auto put = [&](int b) {
+    vm_wait<0>();
+    __syncthreads();                            // the staging rings are done: their memory is reused
+    bool all_ci[NCI];                           // ncig = cit / nci exactly: no ragged ci group here
 #pragma unroll
-            for (int t2 = 0; t2 < NCO; ++t2)
-#pragma unroll
-                for (int u = 0; u < NCI; ++u)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        red[b][(t2 * NCI + u) * 4 + q][lane] = acc[t2][u][q];
-        };
-        auto add = [&](int b) {
-#pragma unroll
-            for (int t2 = 0; t2 < NCO; ++t2)
-#pragma unroll
-                for (int u = 0; u < NCI; ++u)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        acc[t2][u][q] += red[b][(t2 * NCI + u) * 4 + q][lane];
-        };
-        if (wave & 1)
-            put(wave >> 1);
-        __syncthreads();
-        if (!(wave & 1))
-            add(wave >> 1);
-        __syncthreads();
-        if (wave == 2)
-            put(0);
-        __syncthreads();
-        if (wave != 0)
-            return;
-        add(0);
-    }
-    const float inv = 1.0f / (sx * sg);
-    float *out = a.part + (size_t)xsplit * a.Cout * a.Cin;
-#pragma unroll
-    for (int t2 = 0; t2 < NCO; ++t2)
-#pragma unroll
-        for (int u = 0; u < NCI; ++u)
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                out[(size_t)(co0 + 16 * t2 + 4 * q4 + q) * a.Cin + ci0 + 16 * u + j] = acc[t2][u][q] * inv;
+    for (int u = 0; u < NCI; ++u)
+        all_ci[u] = true;
+    wgrad_reduce_store(acc, (float(*)[NREG][64])smem, wave, lane, a.part, xsplit, a.Cout, a.Cin, co0, ci0, all_ci, q4, j, sx, sg);
 }
 
 // dw[i] = sum_s part[s][i], slabs added in fixed order (8 partial sums combined in order through LDS)
@@ -852,44 +620,36 @@ W1Plan w1_plan(int N, int Cin, int Cout, int H, int W)
 
 }  // namespace
 
-bool dcl_wgrad_dma_supported(int nco, int nci) { return nco >= 1 && nco <= 3 && nci >= 1 && nci <= 2; }
+bool dcl_wgrad_dma_supported(int nco, int nci) { return nco >= 1 && nco <= 3 && nci >= 1 && nci <= 2 && nco * nci <= 4; }
 bool dcl_wgrad_dma_wave_mode_supported(int nco, int nci) { return nco == 3 && nci == 1; }
 
-void dcl_wgrad_dma_launch(const WgradArgs &a, int nco, int nci, dim3 grid, hipStream_t s)
+int dcl_wgrad_dma_launch(const WgradArgs &a, int nco, int nci, dim3 grid, hipStream_t s)
 {
-    if (a.pre_sc) {             // the input operand through the producer norm's map + ReLU (k_wgrad3x3d, PRE)
-        if (a.wave_mode) {
-            hipLaunchKernelGGL((k_wgrad3x3d<3, 1, true, true>), dim3(256), dim3(256), 0, s, a);
-            dcl_note_kernel("k_wgrad3x3d_pre<3,1,true>");
-            return;
-        }
-#define DCL_WGD_CASE(o, i)       \
-    if (nco == o && nci == i)    \
-        hipLaunchKernelGGL((k_wgrad3x3d<o, i, false, true>), grid, dim3(256), 0, s, a);
-        DCL_WGD_CASE(2, 2)
-        DCL_WGD_CASE(1, 2)
-        DCL_WGD_CASE(3, 1)
-        DCL_WGD_CASE(2, 1)
-        DCL_WGD_CASE(1, 1)
-#undef DCL_WGD_CASE
-        dcl_note_kernel("k_wgrad3x3d_pre<%d,%d,false>", nco, nci);
-        return;
-    }
+    const bool pre = a.pre_sc != nullptr;       // the input operand through the producer norm's map + ReLU (k_wgrad3x3d, PRE)
     if (a.wave_mode) {
-        hipLaunchKernelGGL((k_wgrad3x3d<3, 1, true>), dim3(256), dim3(256), 0, s, a);
-        dcl_note_kernel("k_wgrad3x3d<3,1,true>");
-        return;
+        if (pre)
+            hipLaunchKernelGGL((k_wgrad3x3d<3, 1, true, true>), dim3(256), dim3(256), 0, s, a);
+        else
+            hipLaunchKernelGGL((k_wgrad3x3d<3, 1, true>), dim3(256), dim3(256), 0, s, a);
+        dcl_note_kernel(pre ? "k_wgrad3x3d_pre<3,1,true>" : "k_wgrad3x3d<3,1,true>");
+        return 0;
     }
-#define DCL_WGD_CASE(o, i)       \
-    if (nco == o && nci == i)    \
-        hipLaunchKernelGGL((k_wgrad3x3d<o, i>), grid, dim3(256), 0, s, a);
+#define DCL_WGD_CASE(o, i)                                                                   \
+    if (nco == o && nci == i) {                                                              \
+        if (pre)                                                                             \
+            hipLaunchKernelGGL((k_wgrad3x3d<o, i, false, true>), grid, dim3(256), 0, s, a);  \
+        else                                                                                 \
+            hipLaunchKernelGGL((k_wgrad3x3d<o, i>), grid, dim3(256), 0, s, a);               \
+    } else
     DCL_WGD_CASE(2, 2)
     DCL_WGD_CASE(1, 2)
     DCL_WGD_CASE(3, 1)
     DCL_WGD_CASE(2, 1)
     DCL_WGD_CASE(1, 1)
+    DCL_WGRAD_NO_KERNEL("k_wgrad3x3d", nco, nci);
 #undef DCL_WGD_CASE
-    dcl_note_kernel("k_wgrad3x3d<%d,%d,false>", nco, nci);
+    dcl_note_kernel(pre ? "k_wgrad3x3d_pre<%d,%d,false>" : "k_wgrad3x3d<%d,%d,false>", nco, nci);
+    return 0;
 }
 
 extern "C" int dcl_wgrad1x1_splits(int N, int Cin, int Cout, int H, int W)
@@ -919,7 +679,8 @@ extern "C" int dcl_wgrad1x1_f16x3(const float *x, const float *dy, int N, int Ci
     hipStream_t s = (hipStream_t)stream;
 #define DCL_W1_CASE(o, i)            \
     if (p.nco == o && p.nci == i)    \
-        hipLaunchKernelGGL((k_wgrad1x1d<o, i>), grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL((k_wgrad1x1d<o, i>), grid, dim3(256), 0, s, a); \
+    else
 #define DCL_W1_ROW(o) DCL_W1_CASE(o, 1) DCL_W1_CASE(o, 2) DCL_W1_CASE(o, 3)
     DCL_W1_ROW(1)
     DCL_W1_ROW(2)
@@ -928,6 +689,7 @@ extern "C" int dcl_wgrad1x1_f16x3(const float *x, const float *dy, int N, int Ci
     DCL_W1_CASE(1, 4)
     DCL_W1_CASE(2, 4)
     DCL_W1_CASE(3, 4)
+    DCL_WGRAD_NO_KERNEL("k_wgrad1x1d", p.nco, p.nci);
 #undef DCL_W1_ROW
 #undef DCL_W1_CASE
     dcl_note_kernel("k_wgrad1x1d<%d,%d>", p.nco, p.nci);

@@ -88,6 +88,14 @@ def conv1x1_wgrad_supported(x, cout):
         and max(x.shape[1], cout) * x.shape[2] * x.shape[3] * 4 < (1 << 32)
 
 
+def _wgrad_buffers(name, splits, co, ci, k, device):
+    """slab workspace (``splits`` slabs, the count the library plans for the shape) and dw [Co, Ci, k, k] of a weight-gradient call"""
+    if splits <= 0:
+        raise RuntimeError(f"{name}: unsupported shape")
+    part = torch.empty(splits * k * k * co * ci, dtype=torch.float32, device=device)
+    return part, torch.empty((co, ci, k, k), dtype=torch.float32, device=device)
+
+
 def conv1x1_wgrad(x, gy):
     """dw [Co, Ci, 1, 1] of a 1x1 convolution, f16x3 (csrc/dcl_wgrad3x3d.hip, k_wgrad1x1d)."""
     from .. import _lib
@@ -95,11 +103,7 @@ def conv1x1_wgrad(x, gy):
     n, ci, h, w = x.shape
     co = gy.shape[1]
     L = _lib.lib()
-    splits = L.dcl_wgrad1x1_splits(n, ci, co, h, w)
-    if splits <= 0:
-        raise RuntimeError("conv1x1_wgrad: unsupported shape")
-    part = torch.empty(splits * co * ci, dtype=torch.float32, device=x.device)
-    dw = torch.empty((co, ci, 1, 1), dtype=torch.float32, device=x.device)
+    part, dw = _wgrad_buffers("conv1x1_wgrad", L.dcl_wgrad1x1_splits(n, ci, co, h, w), co, ci, 1, x.device)
     xa, ga = amax_of(x), amax_of(gy)
     _lib.check(L.dcl_wgrad1x1_f16x3(_lib.ptr(x), _lib.ptr(gy), n, ci, co, h, w, _lib.ptr(xa), xa.numel(),
                                     _lib.ptr(ga), ga.numel(), _lib.ptr(part), _lib.ptr(dw), _stream(x)),
@@ -174,11 +178,7 @@ def conv3x3_wgrad(x, gy, stride=1):
     n, ci, h, w = x.shape
     co = gy.shape[1]
     L = _lib.lib()
-    splits = L.dcl_wgrad3x3_splits(n, ci, co, h, w, stride)
-    if splits <= 0:
-        raise RuntimeError("conv3x3_wgrad: unsupported shape")
-    part = torch.empty(splits * 9 * co * ci, dtype=torch.float32, device=x.device)
-    dw = torch.empty((co, ci, 3, 3), dtype=torch.float32, device=x.device)
+    part, dw = _wgrad_buffers("conv3x3_wgrad", L.dcl_wgrad3x3_splits(n, ci, co, h, w, stride), co, ci, 3, x.device)
     xa, ga = amax_of(x), amax_of(gy)
     assert gy.shape[2] == (h - 1) // stride + 1 and gy.shape[3] == (w - 1) // stride + 1
     _lib.check(L.dcl_wgrad3x3_f16x3(_lib.ptr(x), _lib.ptr(gy), n, ci, co, h, w, _lib.ptr(xa), xa.numel(),
@@ -195,11 +195,7 @@ def conv3x3_wgrad_pre(x, gy, pre_sc, pre_sh, pre_amax, stride=1):
     n, ci, h, w = x.shape
     co = gy.shape[1]
     L = _lib.lib()
-    splits = L.dcl_wgrad3x3_splits(n, ci, co, h, w, stride)
-    if splits <= 0:
-        raise RuntimeError("conv3x3_wgrad_pre: unsupported shape")
-    part = torch.empty(splits * 9 * co * ci, dtype=torch.float32, device=x.device)
-    dw = torch.empty((co, ci, 3, 3), dtype=torch.float32, device=x.device)
+    part, dw = _wgrad_buffers("conv3x3_wgrad_pre", L.dcl_wgrad3x3_splits(n, ci, co, h, w, stride), co, ci, 3, x.device)
     ga = amax_of(gy)
     _lib.check(L.dcl_wgrad3x3_pre_f16x3(_lib.ptr(x), _lib.ptr(gy), n, ci, co, h, w, _lib.ptr(pre_amax), pre_amax.numel(),
                                         _lib.ptr(ga), ga.numel(), _lib.ptr(pre_sc), _lib.ptr(pre_sh), stride, _lib.ptr(part),

@@ -896,7 +896,18 @@ def test_weight_gradient_kernel_variants_match_fp64(dev, variant):
             gw = ops.conv3x3_wgrad(x, gy)
             assert ((gw.double() - ref).abs().max() / ref.abs().max()).item() < 3e-6, (variant, n, ci, co, h, w)
             assert torch.equal(gw, ops.conv3x3_wgrad(x, gy))
+        # a tile without an instantiated kernel is refused and the choice in force stays: (3, 1) plans 42 slabs here, (2, 1) 28
+        auto = L.dcl_wgrad3x3_splits(12, 48, 96, 128, 256, 1)
+        assert L.dcl_wgrad3x3_set_tile(2, 1) == 0
+        forced = L.dcl_wgrad3x3_splits(12, 48, 96, 128, 256, 1)
+        assert forced != auto
+        assert L.dcl_wgrad3x3_set_tile(5, 1) != 0
+        assert L.dcl_wgrad3x3_splits(12, 48, 96, 128, 256, 1) == forced
+        # two ci tiles forced beside the automatic three co tiles would be the retired six-tile wave: the plan keeps (3, 1)
+        assert L.dcl_wgrad3x3_set_tile(0, 2) == 0
+        assert L.dcl_wgrad3x3_splits(12, 48, 96, 128, 256, 1) == auto
     finally:
+        L.dcl_wgrad3x3_set_tile(0, 0)
         L.dcl_wgrad3x3_set_variant(-1)
 
 
