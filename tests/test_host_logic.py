@@ -159,3 +159,43 @@ def test_tapup_support_query_needs_no_gpu():
         assert L.dcl_tapup_supported(20, 20, 0, 0, 160, 160, ac) == 1            # Swin-L at 640 x 640, one source
         assert L.dcl_tapup_supported(64, 16384, 0, 0, 256, 65536, ac) == 0
     assert L.dcl_tapup_supported(0, 4, 0, 0, 8, 8, 0) == 0
+
+
+def test_every_entry_point_has_a_footprint_case_or_a_reason():
+    """tests/test_kernel_footprint.py keeps COVERED (entry points it calls on guarded buffers) and EXEMPT = {name: reason}: together
+    they are exactly the bound entry points, nothing that takes a stream is exempt, and every covered name is
+    CALLED by a test function of that file (directly or through a helper the test names) -- a new entry point cannot be added
+    without a footprint case."""
+    import ast
+    import test_kernel_footprint as fp
+    covered, exempt = set(fp.COVERED), dict(fp.EXEMPT)
+    assert len(covered) == len(fp.COVERED), "COVERED lists a name twice"
+    assert not covered & set(exempt), sorted(covered & set(exempt))
+    assert covered | set(exempt) == set(_lib.SIGNATURES), (sorted(set(_lib.SIGNATURES) - covered - set(exempt)),
+                                                           sorted((covered | set(exempt)) - set(_lib.SIGNATURES)))
+    # an exempt entry does no device work.  What launches work takes a stream as its LAST argument, so a void * there needs a case;
+    # the one entry whose last void * is something else is named here, with what that pointer is
+    not_a_stream = {"dcl_host_randperm_select": "sel_host"}
+    for name, reason in exempt.items():
+        assert isinstance(reason, str) and reason.startswith("host only"), (name, reason)
+        sig = _lib.SIGNATURES[name]
+        if sig and sig[-1] is ctypes.c_void_p:
+            assert name in not_a_stream and not_a_stream[name] in reason and "not a stream" in reason, \
+                f"{name} ends in a void * (a stream: device work): it needs a footprint case, not an exemption"
+    hdr = open(os.path.join(ROOT, "include", "dcl_hip.h")).read()
+    for name in not_a_stream:
+        decl = re.search(rf"\b{name}\s*\(([^;]*)\);", hdr).group(1)
+        assert "stream" not in decl and decl.rstrip().endswith(not_a_stream[name]), decl
+    src = open(fp.__file__).read()
+    funcs = {f.name: ast.get_source_segment(src, f) for f in ast.parse(src).body if isinstance(f, ast.FunctionDef)}
+
+    def reach(name, seen):
+        """the source of a function and of the module-level helpers it names, transitively"""
+        if name in seen:
+            return ""
+        seen.add(name)
+        text = funcs[name]
+        return text + "".join(reach(h, seen) for h in funcs if h != name and re.search(rf"\b{h}\(", text))
+    called = "".join(reach(t, set()) for t in funcs if t.startswith("test_"))
+    missing = [n for n in sorted(covered) if not re.search(rf"\bL\.{n}\(", called)]
+    assert not missing, f"COVERED names no test function calls: {missing}"
