@@ -1,0 +1,29 @@
+// dcl_attn_capi.cpp -- host-only entries of libdcl_attn.so (include/dcl_attn.h): error text, version, shape test, workspace size.
+#include <stdarg.h>
+#include <stdio.h>
+
+#include "dcl_attn_plan.h"
+
+static thread_local char g_err[512] = "";
+
+void dat_set_error(const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+}
+
+extern "C" const char *dat_last_error(void) { return g_err; }
+
+extern "C" int dat_version(void) { return 1; }
+
+extern "C" int dat_supported(int B, int N, int heads, int D) { return dat_shape_ok(B, N, heads, D) ? 1 : 0; }
+
+extern "C" int64_t dat_workspace_bytes(int B, int N, int heads, int D, int backward)
+{
+    DatLayout lay;
+    if (!dat_layout(B, N, heads, D, backward, &lay))
+        return -1;
+    return lay.bytes;
+}

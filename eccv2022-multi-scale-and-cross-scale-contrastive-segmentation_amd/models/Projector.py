@@ -1,8 +1,9 @@
 """Per-scale projection head: 1x1-conv MLP from backbone features to the d-dimensional embedding
 the contrastive loss samples from.  Drop-in for the reference class (models/Projector.py:7-91):
 same config keys (``d``, ``c_in`` int | list, ``mlp`` [[k, c, s], ...] with c = -1 meaning c_in,
-``use_bn``), same sub-module names (``project`` / ``project{s}``) and Sequential indices, hence the
-same state_dict keys; list in -> list out."""
+``use_bn``, ``trans`` / ``heads``), same sub-module names (``project`` / ``project{s}``) and Sequential indices,
+hence the same state_dict keys; list in -> list out.  ``trans: true`` appends a global SelfAttention block
+(models/Transformers.py) between the MLP and the last 1x1 convolution, as the reference does."""
 from typing import Union
 
 import torch
@@ -36,7 +37,14 @@ class LazyProjection:
     def float(self):
         return self
 
+    def _pixel_major(self) -> bool:
+        from .ops_attn import is_pixel_major
+        return is_pixel_major(self.hidden)
+
     def materialize(self) -> torch.Tensor:
+        if self._pixel_major() and self.hidden.is_cuda:
+            from .ops_attn import conv1x1_pixel_major
+            return conv1x1_pixel_major(self.hidden, self.conv)
         return self.conv(self.hidden)
 
     def rows(self, pair_b: torch.Tensor, pix: torch.Tensor) -> torch.Tensor:
@@ -45,7 +53,10 @@ class LazyProjection:
         n, c, h, w = self.hidden.shape
         T, V = pix.shape
         b = pair_b.long().view(T, 1).expand(T, V).reshape(-1)
-        hs = self.hidden.reshape(n, c, h * w)[b, :, pix.long().reshape(-1)]
+        if self._pixel_major():                           # the attention block's output: one contiguous row per pixel
+            hs = self.hidden.permute(0, 2, 3, 1).reshape(n, h * w, c)[b, pix.long().reshape(-1)]
+        else:
+            hs = self.hidden.reshape(n, c, h * w)[b, :, pix.long().reshape(-1)]
         wt = self.conv.weight.view(self.conv.out_channels, c)
         return torch.addmm(self.conv.bias, hs, wt.t()) if self.conv.bias is not None else hs @ wt.t()
 
@@ -61,9 +72,7 @@ class Projector(nn.Module):
         self.mlp = config['mlp'] if 'mlp' in config else []
         self.use_bn = config['use_bn'] if 'use_bn' in config else False
         self.transformer = config['trans'] if 'trans' in config else False
-        if self.transformer:
-            raise NotImplementedError("Projector(trans=True) is not part of the MI355X hot path "
-                                      "(no shipped config uses it; reference: models/Transformers.py)")
+        self.heads = config['heads'] if 'heads' in config else 1
         assert isinstance(self.mlp, list), 'config["mlp"] must be [[k_1, c_1, s_1], ..., [k_n, c_n, s_n]] or []'
         for layer in self.mlp:
             assert isinstance(layer, list) and len(layer) == 3 and layer[2] in [1, 2], \
@@ -89,6 +98,10 @@ class Projector(nn.Module):
             if self.use_bn:
                 layers.append(nn.BatchNorm2d(c_out, momentum=0.0003))
             c_prev = c_out
+        if self.transformer:
+            from .Transformers import SelfAttention
+            layers.append(SelfAttention(dim=c_prev, heads=self.heads))
+            printlog(f'Projector creating transformer layer, heads_{self.heads}/c_{c_prev}')
         layers.append(nn.Conv2d(c_prev, self.d, kernel_size=1, stride=1))
         printlog(f'Projector head {c_in} -> {self.d} ({len(self.mlp)} hidden layer(s), bn={self.use_bn})')
         return nn.Sequential(*layers)
@@ -114,6 +127,14 @@ class Projector(nn.Module):
         return x
 
     def _run_head(self, head: nn.Sequential, x: torch.Tensor):
+        if self.transformer and x.is_cuda and x.dtype == torch.float32:
+            # the attention block hands a pixel-major hidden map on (reference quirk, models/Transformers.py): the last 1x1
+            # convolution is a Linear over its rows, and its result is pixel-major in every return mode
+            from .ops_attn import conv1x1_pixel_major, is_pixel_major
+            hidden = self._hidden(head, x)
+            if self.lazy and self.training:
+                return LazyProjection(hidden, head[-1])
+            return conv1x1_pixel_major(hidden, head[-1]) if is_pixel_major(hidden) else head[-1](hidden)
         if self.lazy and self.training and x.is_cuda and x.dtype == torch.float32:
             return LazyProjection(self._hidden(head, x), head[-1])
         if self.nhwc and self.training and x.is_cuda and torch.is_grad_enabled():
