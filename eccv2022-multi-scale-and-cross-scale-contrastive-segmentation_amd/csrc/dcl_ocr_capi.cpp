@@ -1,0 +1,25 @@
+// dcl_ocr_capi.cpp -- host-only entries of libdcl_ocr.so (include/dcl_ocr.h): error text, version, shape test, workspace size.
+#include <stdarg.h>
+#include <stdio.h>
+
+#include "dcl_ocr_plan.h"
+
+static thread_local char g_err[512] = "";
+
+void dco_set_error(const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+}
+
+extern "C" const char *dco_last_error(void) { return g_err; }
+
+extern "C" int dco_version(void) { return 1; }
+
+extern "C" int dco_supported(int B, int C, int K, int N) { return dco_shape_ok(B, C, K, N) ? 1 : 0; }
+
+extern "C" int dco_splits(int B, int C, int N) { return dco_shape_ok(B, C, 1, N) ? dco_split_count(B, C, N) : 0; }
+
+extern "C" int64_t dco_workspace_bytes(int op, int B, int C, int K, int N) { return dco_ws_bytes(op, B, C, K, N); }
