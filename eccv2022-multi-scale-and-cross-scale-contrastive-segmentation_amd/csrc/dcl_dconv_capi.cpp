@@ -1,0 +1,36 @@
+// dcl_dconv_capi.cpp -- host-only entries of libdcl_dconv.so (include/dcl_dconv.h): error text, version, shape test, live taps,
+// slab count, workspace and fragment sizes.
+#include <stdarg.h>
+#include <stdio.h>
+
+#include "dcl_dconv_plan.h"
+
+static thread_local char g_err[512] = "";
+
+void ddc_set_error(const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+}
+
+extern "C" const char *ddc_last_error(void) { return g_err; }
+
+extern "C" int ddc_version(void) { return 1; }
+
+extern "C" int ddc_supported(int N, int Ci, int Co, int H, int W, int d) { return ddc_shape_ok(N, Ci, Co, H, W, d) ? 1 : 0; }
+
+extern "C" unsigned ddc_live_taps(int H, int W, int d) { return ddc_live_mask(H, W, d); }
+
+extern "C" int ddc_wgrad_slabs(int N, int Ci, int Co, int H, int W, int d)
+{
+    return ddc_shape_ok(N, Ci, Co, H, W, d) ? ddc_slab_count(N, Ci, Co, H, W, d) : 0;
+}
+
+extern "C" int64_t ddc_workspace_bytes(int op, int N, int Ci, int Co, int H, int W, int d)
+{
+    return ddc_ws_bytes(op, N, Ci, Co, H, W, d);
+}
+
+extern "C" int64_t ddc_packed_bytes(int Co, int Ci, int transposed) { return ddc_pack_bytes(Co, Ci, transposed); }
