@@ -65,6 +65,7 @@ class DebugConfig:
     attn_hip: bool = field(default_factory=lambda: _flag('DCL_ATTN_HIP'))                       # Projector(trans) attention on libdcl_attn.so; 0 = PyTorch
     ocr_hip: bool = field(default_factory=lambda: _flag('DCL_OCR_HIP'))                         # OCRNet context core on libdcl_ocr.so; 0 = PyTorch
     dconv_hip: bool = field(default_factory=lambda: _flag('DCL_DCONV_HIP'))                     # DeepLabv3's dilated 3x3 convolutions on libdcl_dconv.so; 0 = PyTorch
+    tta_hip: bool = field(default_factory=lambda: _flag('DCL_TTA_HIP'))                         # test-time-augmentation merge on libdcl_tta.so; 0 = PyTorch
     # ---- kernel variants set on the library at load (include/dcl_hip.h "tuning hook" entries)
     wgrad_variant: Optional[int] = field(default_factory=lambda: _int('DCL_WGRAD_VARIANT'))
     wgrad_wg_target: Optional[int] = field(default_factory=lambda: _int('DCL_WGRAD_TARGET'))    # workgroups a weight-gradient launch aims at

@@ -440,6 +440,60 @@ class BaseManager:
         self.model.train()
         return miou
 
+    def _tta_model(self):
+        """The reference's dispatch (BaseManager.py:610-635): CITYSCAPES -> TTAWrapperCTS (multi-scale, flip, sliding window),
+        everything without a protocol of its own -> TTAWrapper (multi-scale, flip)."""
+        cfg = self.config
+        scales_list = [0.75, 1.25, 1.5, 1.75, 2] if not self.debugging else [1.0]
+        if 'tta_scales' in cfg and not self.debugging:
+            scales_list = cfg['tta_scales']
+        if self.dataset == 'CITYSCAPES':
+            crop_size = cfg['data']['transform_values']['crop_shape']
+            strides = cfg['strides'] if 'strides' in cfg else crop_size
+            flip = cfg['flip'] if 'flip' in cfg else True
+            return _models.TTAWrapperCTS(self.model, scales_list, flip, strides, crop_size)
+        if self.dataset == 'PASCALC':
+            raise NotImplementedError("TTAWrapperPC (the reference's PASCAL-Context protocol: border padding through cv2) is "
+                                      "not ported; only TTAWrapper and TTAWrapperCTS are (DESIGN.md, 'Test-time augmentation')")
+        if self.dataset == 'ADE20K' and 'strides' in cfg:
+            raise NotImplementedError("TTAWrapperSlide (the reference's ADE20K sliding-window protocol: every image resized to a "
+                                      "hard-coded (2048 s, 512 s)) is not ported; drop `strides` from the config for TTAWrapper")
+        return _models.TTAWrapper(self.model, scales_list)
+
+    @torch.no_grad()
+    def infer(self):
+        """Run the model over ``valid_loader`` the way the reference's ``infer()`` does (BaseManager.py:585-675): the checkpoint
+        named by ``load_checkpoint`` (``load_last``: the last instead of the best one), with ``tta`` the model inside a test-time
+        augmentation wrapper (``tta_scales``, ``strides``, ``flip``, ``data.transform_values.crop_shape``), the confusion matrix
+        summed over the images.  Returns the metrics dict of ``t_get_mean_iou`` and logs the mIoU on rank 0.  No
+        ``post_process_output`` step and no saved images."""
+        cfg = self.config
+        assert 'load_checkpoint' in cfg, 'load_checkpoint: "run_id" must be in config for inference mode!'
+        self.model.eval()
+        bare = self._bare_model()
+        for flag in ('get_intermediate', 'return_features'):       # suppress the auxiliary output and the projector's features
+            if hasattr(bare, flag):
+                setattr(bare, flag, False)
+        self.load_checkpoint(cfg['load_checkpoint'], 'last' if cfg.get('load_last', False) else 'best')
+        tta_model = None
+        if cfg['tta']:
+            tta_model = self._tta_model()
+            printlog(f'** {tta_model.__class__.__name__} using tta with transforms \n ** flip and scales: {tta_model.scales}')
+        confusion_matrix = None
+        for rec_num, batch in enumerate(self.data_loaders['valid_loader']):
+            img, lbl = batch[0].to(self.device), batch[1].to(self.device)
+            output = tta_model(img.float()) if tta_model is not None else bare(img.float())
+            confusion_matrix = t_get_confusion_matrix(output, lbl, self.dataset, confusion_matrix)
+            if rec_num == 10 and self.debugging:
+                break
+        mious = t_get_mean_iou(confusion_matrix, self.experiment, self.dataset, True, rare=True)
+        if self.rank == 0:
+            msg_str = "miou:{:.4f} ".format(float(mious['mean_iou']))
+            for categ, v in mious['categories'].items():
+                msg_str += "- {}:{:.4f}".format(categ, float(v))
+            printlog(msg_str)
+        return mious
+
     # ------------------------------------------------------------------ checkpoints
     def _log_dir(self):
         """``<log_path>/<run_id>`` like the reference (LoggingManager.py:81-91); created on first use so that runs

@@ -586,6 +586,7 @@ class HRNet(nn.Module):
         name = config.get('backbone', 'hrnet48')
         self.backbone_name = name if name in _FACTORIES else 'hrnet48'
         self.out_stride = 4
+        self.lazy_eval_logits = False
         self.dataset = config['dataset']
         # fused BN(+add)(+ReLU) kernels (models/fused_bn.py); same parameters / state_dict as nn.BatchNorm2d
         self.norm = FusedBatchNorm2d if config.get('fused_bn', True) else nn.BatchNorm2d
@@ -699,9 +700,10 @@ class HRNet(nn.Module):
         feats = self.backbone(x)
         multi = self.use_ms_projector or self.return_backbone_feats
         logits = self._head(feats[0] if multi else feats)
-        if self.config.get('lazy_logits', False) and self.training:
+        if (self.config.get('lazy_logits', False) and self.training) or self.lazy_eval_logits:
             # extension (default off = the reference's return value): the logits stay at 1/4 resolution; this repo's
-            # LossWrapper / metrics apply up-sampling + cross-entropy / arg-max in fused kernels (models/ops.py)
+            # LossWrapper / metrics apply up-sampling + cross-entropy / arg-max in fused kernels (models/ops.py);
+            # lazy_eval_logits: the same in eval mode, set by the test-time-augmentation wrappers around their calls (models/TTA.py)
             from .ops import UpsampledLogits
             logits = UpsampledLogits(logits, size, self.align_corners)
         else:

@@ -191,6 +191,7 @@ class UPerNet(nn.Module):
         self.config = config
         self.experiment = experiment
         self.out_stride = 32
+        self.lazy_eval_logits = False
         self.dataset = config['dataset']
         self.backbone_name = config['backbone']
         self.norm = FusedBatchNorm2d if config.get('hip_decoder', True) else nn.BatchNorm2d
@@ -316,7 +317,8 @@ class UPerNet(nn.Module):
         # graph key `lazy_logits` (extension, default off = the reference's return values): the logits of both heads stay
         # at their own resolution; this repo's LossWrapper / TwoScaleLoss / metrics apply up-sampling + cross-entropy /
         # arg-max in fused kernels (models/ops.py UpsampledLogits) -- 2 x 16 x 150 x 512 x 512 floats are never written
-        lazy = self.config.get('lazy_logits', False) and self.training and logits.is_cuda
+        # (lazy_eval_logits: the same in eval mode, set by the test-time-augmentation wrappers around their calls, models/TTA.py)
+        lazy = (self.config.get('lazy_logits', False) and self.training and logits.is_cuda) or self.lazy_eval_logits
         if lazy:
             from .ops import UpsampledLogits
             up = lambda t: UpsampledLogits(t, size, self.align_corners)
