@@ -199,10 +199,8 @@ class BaseManager:
 
     def load_data(self):
         dcfg = self.config['data']
-        if not dcfg.get('synthetic', False):
-            raise NotImplementedError(
-                "only data.synthetic=true is available: real Cityscapes / ADE20K loaders "
-                "(reference datasets/*.py) are outside the accelerated hot path (SURVEY.md row 15)")
+        if dcfg.get('synthetic_raw', False) or not dcfg.get('synthetic', False):
+            return self._load_raw_data()
         names = DATASETS_INFO[self.dataset].CLASS_INFO[self.experiment][1]
         size = dcfg.get('transform_values', {}).get('crop_shape', [512, 1024])
         train = SyntheticSegmentation(dcfg.get('synthetic_length', 64), size, len(names),
@@ -216,6 +214,47 @@ class BaseManager:
             num_workers=dcfg['num_workers'], drop_last=True, pin_memory=self.device.type == 'cuda')
         self.data_loaders['valid_loader'] = DataLoader(valid, batch_size=self.valid_batch_size, shuffle=False,
                                                        num_workers=0)
+        self.train_schedule = {e: 'train_loader' for e in range(self.config['train']['epochs'])}
+
+    def _load_raw_data(self):
+        """The raw input path (datasets/raw.py, datasets/augment.py): the loaders only decode files (or draw ``synthetic_raw``
+        pixels) and attach each sample's augmentation plan; ``_upload`` runs the augmentation on the device."""
+        from ..datasets import ADE20K, AugmentPlanner, Cityscapes, DeviceAugment, SyntheticRaw, list_collate, network_lut
+        dcfg, seed = self.config['data'], self.config['seed']
+        tv = dcfg.get('transform_values', {})
+        plan_t = AugmentPlanner(dcfg.get('transforms', ['RandomCropImgLbl', 'torchvision_normalise']), tv, self.dataset,
+                                self.experiment, seed)
+        plan_v = AugmentPlanner(dcfg.get('transforms_val', ['torchvision_normalise']), dcfg.get('transform_values_val', tv),
+                                self.dataset, self.experiment, seed + 1)
+        if plan_v.resize_val:
+            printlog("[mscs_amd] transforms_val holds resize_val: validate() will raise (the reference's original-label "
+                     "evaluation is not ported)")
+        if dcfg.get('synthetic_raw', False):
+            size = dcfg.get('synthetic_raw_size', [1024, 2048])
+            train = SyntheticRaw(dcfg.get('synthetic_length', 64), size, self.dataset, self.experiment, plan_t, seed=seed)
+            valid = SyntheticRaw(dcfg.get('synthetic_valid_length', 4), size, self.dataset, self.experiment, plan_v, seed=seed + 1)
+        else:
+            if not self.config.get('data_path'):
+                raise KeyError("data_path: the config names no dataset folder (set data_path, or data.synthetic / "
+                               "data.synthetic_raw for generated data)")
+            root = self.config['data_path']
+            # data.split = [train split, validation split] as in the reference's configs (its managers/BaseManager.py load_data)
+            if self.dataset == 'CITYSCAPES':
+                split = dcfg.get('split', ['train', 'val'])
+                train, valid = Cityscapes(root, split[0], plan_t), Cityscapes(root, split[1], plan_v)
+            elif self.dataset == 'ADE20K':
+                split = dcfg.get('split', ['train', 'val'])
+                train, valid = ADE20K(root, split[0], plan_t), ADE20K(root, split[1], plan_v)
+            else:
+                raise NotImplementedError(f"no reader for dataset {self.dataset}: CITYSCAPES and ADE20K are ported (SURVEY.md row 15)")
+        self._augment = DeviceAugment(network_lut(self.dataset, self.experiment))
+        sampler = DistributedSampler(train, num_replicas=self.world_size, rank=self.rank) if self.parallel else None
+        self.samplers['train_loader'] = sampler
+        self.data_loaders['train_loader'] = DataLoader(
+            train, batch_size=self.batch_size, shuffle=sampler is None, sampler=sampler, num_workers=dcfg['num_workers'],
+            drop_last=True, pin_memory=self.device.type == 'cuda', collate_fn=list_collate)
+        self.data_loaders['valid_loader'] = DataLoader(valid, batch_size=self.valid_batch_size, shuffle=False, num_workers=0,
+                                                       collate_fn=list_collate)
         self.train_schedule = {e: 'train_loader' for e in range(self.config['train']['epochs'])}
 
     def _param_groups(self):
@@ -295,24 +334,37 @@ class BaseManager:
             sampler = self.samplers.get(self.train_schedule[self.epoch])
             if sampler is not None:
                 sampler.set_epoch(self.epoch)
+            dataset = self.data_loaders[self.train_schedule[self.epoch]].dataset
+            if hasattr(dataset, 'set_epoch'):           # raw path: the epoch of the augmentation plans' stream
+                dataset.set_epoch(self.epoch)
             self.train_one_epoch()
             if (self.epoch + 1) % self.config.get('valid_freq', 1) == 0 or self.epoch == tcfg['epochs'] - 1:
                 self.validate()
         if self.parallel and dist.is_initialized():
             dist.barrier()
 
-    def _upload(self, img, lbl):
+    def _upload(self, img, lbl, meta=None):
         """H2D of a batch on a dedicated input stream (+ the label's int64 conversion), and the event that marks
         it complete: the loss's label stage waits for THAT event only (engine.stage_labels), so it -- and the host
-        plan built from it -- can run while the GPU is still in the previous step's backward."""
+        plan built from it -- can run while the GPU is still in the previous step's backward.  A raw batch (lists of
+        decoded uint8 tensors, the plans in ``meta``) is copied as it is and augmented on the same stream
+        (datasets/augment.py DeviceAugment) before the event is recorded."""
+        raw = isinstance(img, (list, tuple))
+        plans = [m['plan'] for m in meta] if raw else None
         if self.device.type != 'cuda':
+            if raw:
+                return (*self._augment(list(img), list(lbl), plans), None)
             return img.to(self.device), lbl.to(self.device), None
         if getattr(self, '_in_stream', None) is None:
             self._in_stream = torch.cuda.Stream(device=self.device, priority=-1)    # own hardware queue
         cur = torch.cuda.current_stream(self.device)
         with torch.cuda.stream(self._in_stream):
-            img = img.to(self.device, non_blocking=True)
-            lbl = lbl.to(self.device, non_blocking=True).long()
+            if raw:
+                img, lbl = self._augment([t.to(self.device, non_blocking=True) for t in img],
+                                         [t.to(self.device, non_blocking=True) for t in lbl], plans)
+            else:
+                img = img.to(self.device, non_blocking=True)
+                lbl = lbl.to(self.device, non_blocking=True).long()
             ready = torch.cuda.Event()
             ready.record(self._in_stream)
         cur.wait_event(ready)
@@ -324,7 +376,7 @@ class BaseManager:
         self.model.train()
         t_prev = time.perf_counter()
         for batch_num, batch in enumerate(self.data_loaders[self.train_schedule[self.epoch]]):
-            img, lbl, ready = self._upload(batch[0], batch[1])
+            img, lbl, ready = self._upload(*batch[:3])
             self.optimiser.zero_grad()
             ret = self.forward_step(img, lbl, label_ready=ready)
             ret['loss'].backward()
@@ -402,6 +454,16 @@ class BaseManager:
             terms = ' '.join(f'{k}:{v:.4f}' for k, v in zip(keys, vals))
             printlog(f'ep {self.epoch} it {batch_num} t:{ms:.0f}ms {terms}')
 
+    def _valid_batch(self, batch):
+        """(img, lbl) of a validation batch on the device; on the raw path through the validation plan's geometry."""
+        if not isinstance(batch[0], (list, tuple)):
+            return batch[0].to(self.device), batch[1].to(self.device)
+        if any((m['plan'].rh, m['plan'].rw) != (m['plan'].H, m['plan'].W) for m in batch[2]):
+            raise NotImplementedError("validation on resize_val needs the reference's original-label evaluation "
+                                      "(Resize(return_original_labels=True)), which is not ported")
+        img, lbl, _ = self._upload(*batch[:3])
+        return img, lbl
+
     @torch.no_grad()
     def validate(self):
         if self.rank != 0:          # rank 0 only, like the reference (HRNet_Manager.py:150-156)
@@ -409,7 +471,7 @@ class BaseManager:
         self.model.eval()
         cm = 0
         for i, batch in enumerate(self.data_loaders['valid_loader']):
-            img, lbl = batch[0].to(self.device), batch[1].to(self.device)
+            img, lbl = self._valid_batch(batch)
             out = self._bare_model()(img.float())
             logits = out[0] if isinstance(out, (tuple, list)) and out[0].dim() == 4 and len(out) == 2 else out
             if isinstance(logits, (tuple, list)):
@@ -481,7 +543,7 @@ class BaseManager:
             printlog(f'** {tta_model.__class__.__name__} using tta with transforms \n ** flip and scales: {tta_model.scales}')
         confusion_matrix = None
         for rec_num, batch in enumerate(self.data_loaders['valid_loader']):
-            img, lbl = batch[0].to(self.device), batch[1].to(self.device)
+            img, lbl = self._valid_batch(batch)
             output = tta_model(img.float()) if tta_model is not None else bare(img.float())
             confusion_matrix = t_get_confusion_matrix(output, lbl, self.dataset, confusion_matrix)
             if rec_num == 10 and self.debugging:
