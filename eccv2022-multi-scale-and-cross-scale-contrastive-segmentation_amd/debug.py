@@ -67,6 +67,7 @@ class DebugConfig:
     dconv_hip: bool = field(default_factory=lambda: _flag('DCL_DCONV_HIP'))                     # DeepLabv3's dilated 3x3 convolutions on libdcl_dconv.so; 0 = PyTorch
     tta_hip: bool = field(default_factory=lambda: _flag('DCL_TTA_HIP'))                         # test-time-augmentation merge on libdcl_tta.so; 0 = PyTorch
     aug_hip: bool = field(default_factory=lambda: _flag('DCL_AUG_HIP'))                         # input augmentation on libdcl_aug.so; 0 = PyTorch
+    pred_hip: bool = field(default_factory=lambda: _flag('DCL_PRED_HIP'))                       # prediction maps on libdcl_pred.so; 0 = PyTorch
     # ---- kernel variants set on the library at load (include/dcl_hip.h "tuning hook" entries)
     wgrad_variant: Optional[int] = field(default_factory=lambda: _int('DCL_WGRAD_VARIANT'))
     wgrad_wg_target: Optional[int] = field(default_factory=lambda: _int('DCL_WGRAD_TARGET'))    # workgroups a weight-gradient launch aims at

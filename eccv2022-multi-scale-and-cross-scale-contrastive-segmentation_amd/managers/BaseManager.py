@@ -470,15 +470,22 @@ class BaseManager:
             return None
         self.model.eval()
         cm = 0
-        for i, batch in enumerate(self.data_loaders['valid_loader']):
-            img, lbl = self._valid_batch(batch)
-            out = self._bare_model()(img.float())
-            logits = out[0] if isinstance(out, (tuple, list)) and out[0].dim() == 4 and len(out) == 2 else out
-            if isinstance(logits, (tuple, list)):
-                logits = logits[1]
-            cm = cm + t_get_confusion_matrix(logits, lbl, self.dataset)
-            if i + 1 >= self.config.get('max_valid_imgs', 10):
-                break
+        panels = self._panel_writer() if self.config.get('save_valid_images', False) else None
+        try:
+            for i, batch in enumerate(self.data_loaders['valid_loader']):
+                img, lbl = self._valid_batch(batch)
+                out = self._bare_model()(img.float())
+                logits = out[0] if isinstance(out, (tuple, list)) and out[0].dim() == 4 and len(out) == 2 else out
+                if isinstance(logits, (tuple, list)):
+                    logits = logits[1]
+                cm = cm + t_get_confusion_matrix(logits, lbl, self.dataset)
+                if panels is not None:
+                    self._save_panel(panels, i, img, lbl, logits)
+                if i + 1 >= self.config.get('max_valid_imgs', 10):
+                    break
+        finally:
+            if panels is not None:
+                panels[0].close()
         miou = float(t_get_mean_iou(cm).item())
         if torch.is_tensor(cm) and cm.is_cuda and int(take_out_of_range(cm.device).item()) > 0:
             # a validation label outside the class range: F.one_hot's error in the reference's confusion matrix
@@ -501,6 +508,53 @@ class BaseManager:
                 self.save_checkpoint(is_best=False)
         self.model.train()
         return miou
+
+    # ------------------------------------------------------------------ saved predictions (utils/predict.py)
+    def _panel_writer(self):
+        """(writer, palette) of ``save_valid_images``: <log_dir>/valid_images/record_NN_stepS.png, one image | label | prediction
+        panel per validation record (the reference's to_comb_image, which it hands to TensorBoard)."""
+        from ..utils.predict import PredictionWriter, class_palette
+        palette = class_palette(self.dataset, self.experiment, self.config['data'].get('palette')).to(self.device)
+        return PredictionWriter(os.path.join(self._log_dir(), 'valid_images'), self.config.get('save_depth', 2)), palette
+
+    def _save_panel(self, panels, rec, img, lbl, logits):
+        from ..utils import ignore_class
+        from ..utils.predict import panel_image, predict_maps
+        writer, palette = panels
+        first = logits.materialize()[:1] if hasattr(logits, 'materialize') else logits[:1]
+        ids = predict_maps(first)[0]
+        ignore = ignore_class(self.dataset, self.experiment)
+        panel = panel_image(img[0].float(), lbl[0], ids[0], palette, label_ignore=ignore, ids_ignore=ignore)
+        writer.write('record_{:02d}_step{}.png'.format(rec, self.global_step), panel)
+
+    @staticmethod
+    def _record_stem(batch, n, index):
+        """File stem of sample ``n`` of a batch: its target_filename, else its img_filename, else record_{index:06d}."""
+        meta = batch[2] if len(batch) > 2 else None
+        if isinstance(meta, (list, tuple)) and n < len(meta):
+            meta = meta[n]
+            n = None
+        if isinstance(meta, dict):
+            for key in ('target_filename', 'img_filename'):
+                name = meta.get(key)
+                if isinstance(name, (list, tuple)) and n is not None and n < len(name):
+                    name = name[n]
+                if isinstance(name, (str, os.PathLike)) and str(name):
+                    return os.path.splitext(os.path.basename(str(name)))[0]
+        return 'record_{:06d}'.format(index)
+
+    @staticmethod
+    def _call_lazy(model, x):
+        """model(x) with ``lazy_eval_logits`` set around the call where the model has it (HRNet, UPerNet: the logits stay at 1/4
+        resolution, as for the test-time-augmentation wrappers, models/TTA.py); restored also when the call raises."""
+        if not hasattr(model, 'lazy_eval_logits'):
+            return model(x)
+        saved = model.lazy_eval_logits
+        model.lazy_eval_logits = True
+        try:
+            return model(x)
+        finally:
+            model.lazy_eval_logits = saved
 
     def _tta_model(self):
         """The reference's dispatch (BaseManager.py:610-635): CITYSCAPES -> TTAWrapperCTS (multi-scale, flip, sliding window),
@@ -528,7 +582,10 @@ class BaseManager:
         named by ``load_checkpoint`` (``load_last``: the last instead of the best one), with ``tta`` the model inside a test-time
         augmentation wrapper (``tta_scales``, ``strides``, ``flip``, ``data.transform_values.crop_shape``), the confusion matrix
         summed over the images.  Returns the metrics dict of ``t_get_mean_iou`` and logs the mIoU on rank 0.  No
-        ``post_process_output`` step and no saved images."""
+        ``post_process_output`` step.  ``save_outputs: true`` (rank 0) writes, per image, the reference's two files
+        (BaseManager.py:677-699): <log_dir>/outputs/<split>/debug/<stem>.png (colours) and .../submit/<stem>.png (dataset class
+        ids), through utils/predict.py: without tta the model is then called with ``lazy_eval_logits`` and prediction and
+        confusion matrix both come from its 1/4-resolution map."""
         cfg = self.config
         assert 'load_checkpoint' in cfg, 'load_checkpoint: "run_id" must be in config for inference mode!'
         self.model.eval()
@@ -542,12 +599,34 @@ class BaseManager:
             tta_model = self._tta_model()
             printlog(f'** {tta_model.__class__.__name__} using tta with transforms \n ** flip and scales: {tta_model.scales}')
         confusion_matrix = None
-        for rec_num, batch in enumerate(self.data_loaders['valid_loader']):
-            img, lbl = self._valid_batch(batch)
-            output = tta_model(img.float()) if tta_model is not None else bare(img.float())
-            confusion_matrix = t_get_confusion_matrix(output, lbl, self.dataset, confusion_matrix)
-            if rec_num == 10 and self.debugging:
-                break
+        writer = None
+        if cfg.get('save_outputs', False) and self.rank == 0:
+            from ..utils.predict import PredictionWriter, class_palette, predict_maps, submission_lut
+            split = cfg['data'].get('split')                        # [train split, validation split]; the parser's default is an int
+            split = split[-1] if isinstance(split, (list, tuple)) and split else 'val'
+            writer = PredictionWriter(os.path.join(self._log_dir(), 'outputs', str(split)), cfg.get('save_depth', 2))
+            lut = submission_lut(self.dataset, self.experiment).to(self.device)
+            palette = class_palette(self.dataset, self.experiment, cfg['data'].get('palette')).to(self.device)
+            saved = 0
+        try:
+            for rec_num, batch in enumerate(self.data_loaders['valid_loader']):
+                img, lbl = self._valid_batch(batch)
+                if writer is None:
+                    output = tta_model(img.float()) if tta_model is not None else bare(img.float())
+                else:
+                    output = tta_model(img.float()) if tta_model is not None else self._call_lazy(bare, img.float())
+                    _, mapped, rgb = predict_maps(output, lut, palette)     # (leaves output.pred for the confusion matrix)
+                    for n in range(mapped.shape[0]):
+                        stem = self._record_stem(batch, n, saved)
+                        writer.write(os.path.join('debug', stem + '.png'), rgb[n])
+                        writer.write(os.path.join('submit', stem + '.png'), mapped[n])
+                        saved += 1
+                confusion_matrix = t_get_confusion_matrix(output, lbl, self.dataset, confusion_matrix)
+                if rec_num == 10 and self.debugging:
+                    break
+        finally:
+            if writer is not None:
+                writer.close()
         mious = t_get_mean_iou(confusion_matrix, self.experiment, self.dataset, True, rare=True)
         if self.rank == 0:
             msg_str = "miou:{:.4f} ".format(float(mious['mean_iou']))
