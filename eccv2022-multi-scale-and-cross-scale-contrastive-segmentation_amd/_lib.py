@@ -148,6 +148,34 @@ def build(verbose: bool = False) -> str:
     return LIB_PATH
 
 
+def load_library(path, signatures, prefix, what, restypes=None):
+    """Load the C-ABI library at ``path`` and type its entries: ``signatures`` maps name -> argtypes, every result is an int
+    except the ``restypes`` (name -> ctypes type), and ``{prefix}_last_error()`` returns the text of the last failed call.
+    A missing library raises: there is no fallback for the ``what`` to take."""
+    if not os.path.exists(path):
+        raise RuntimeError(
+            f"{path} not found. The {what} have no fallback once selected: build the HIP "
+            f"libraries first (python -c 'import __graft_entry__ as g; g.build()' or make -C {CSRC_DIR}).")
+    l = ctypes.CDLL(path)
+    for name, argtypes in signatures.items():
+        fn = getattr(l, name)
+        fn.argtypes = argtypes
+        fn.restype = ctypes.c_int
+    for name, restype in (restypes or {}).items():
+        getattr(l, name).restype = restype
+    last_error = getattr(l, prefix + "_last_error")
+    last_error.restype = ctypes.c_char_p
+    last_error.argtypes = []
+    return l
+
+
+def raise_on_error(rc: int, what: str, last_error_fn):
+    """The body of every binding module's ``check()``: a non-zero return code raises with the library's own error text."""
+    if rc != 0:
+        msg = last_error_fn().decode("utf-8", "replace")
+        raise RuntimeError(f"{what} failed (code {rc}): {msg}")
+
+
 def lib():
     """The loaded library; raises if it has not been built (no CPU fallback exists)."""
     global _lib
@@ -156,27 +184,18 @@ def lib():
             raise RuntimeError(
                 f"{LIB_PATH} not found. The dense contrastive loss has no fallback path: build the HIP "
                 f"library first (python -c 'import __graft_entry__ as g; g.build()' or make -C {CSRC_DIR}).")
-        from .debug import cfg as _dbg0
-        l = ctypes.CDLL(_dbg0.lib_path or LIB_PATH)      # (lib_path: probe builds, tools/probes/conv_bounds.sh)
-        for name, argtypes in SIGNATURES.items():
-            fn = getattr(l, name)
-            fn.argtypes = argtypes
-            fn.restype = ctypes.c_int
-        l.dcl_last_error.restype = ctypes.c_char_p
+        from .debug import cfg as _dbg       # lib_path: probe builds (tools/probes/conv_bounds.sh); A/B switches of the tuning tools
+        l = load_library(_dbg.lib_path or LIB_PATH, SIGNATURES, "dcl", "kernels of the dense contrastive loss",
+                         restypes={"dcl_gemm_workspace_floats": ctypes.c_int64})
         l.dcl_last_kernel.restype = ctypes.c_char_p
         l.dcl_last_kernel.argtypes = []
-        l.dcl_gemm_workspace_floats.restype = ctypes.c_int64
-        l.dcl_last_error.argtypes = []
-        from .debug import cfg as _dbg       # A/B switches of the tuning tools: one object, read once
         _dbg.apply_to_library(l)
         _lib = l
     return _lib
 
 
 def check(rc: int, what: str):
-    if rc != 0:
-        msg = lib().dcl_last_error().decode("utf-8", "replace")
-        raise RuntimeError(f"{what} failed (code {rc}): {msg}")
+    raise_on_error(rc, what, lib().dcl_last_error)
 
 
 def ptr(t):

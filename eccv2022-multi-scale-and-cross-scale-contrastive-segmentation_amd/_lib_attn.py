@@ -6,6 +6,7 @@ import ctypes
 import os
 
 from ._lib import CSRC_DIR, _PKG_DIR, ptr, stream_ptr  # noqa: F401  (re-exported for callers of this module)
+from ._lib import load_library, raise_on_error
 
 LIB_PATH = os.path.join(_PKG_DIR, "libdcl_attn.so")
 MAX_HEAD_DIM = 256    # DAT_MAX_HEAD_DIM
@@ -34,26 +35,13 @@ def lib():
     """The loaded library; raises if it has not been built."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                f"{LIB_PATH} not found. The attention kernels have no fallback once selected: build the HIP "
-                f"libraries first (python -c 'import __graft_entry__ as g; g.build()' or make -C {CSRC_DIR}).")
-        l = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in SIGNATURES.items():
-            fn = getattr(l, name)
-            fn.argtypes = argtypes
-            fn.restype = ctypes.c_int
-        l.dat_workspace_bytes.restype = ctypes.c_int64
-        l.dat_last_error.restype = ctypes.c_char_p
-        l.dat_last_error.argtypes = []
-        _lib = l
+        _lib = load_library(LIB_PATH, SIGNATURES, "dat", "attention kernels",
+                            restypes={"dat_workspace_bytes": _i64})
     return _lib
 
 
 def check(rc: int, what: str):
-    if rc != 0:
-        msg = lib().dat_last_error().decode("utf-8", "replace")
-        raise RuntimeError(f"{what} failed (code {rc}): {msg}")
+    raise_on_error(rc, what, lib().dat_last_error)
 
 
 def supported(b: int, n: int, heads: int, d: int) -> bool:

@@ -6,6 +6,7 @@ import ctypes
 import os
 
 from ._lib import CSRC_DIR, _PKG_DIR, ptr, stream_ptr  # noqa: F401  (re-exported for callers of this module)
+from ._lib import load_library, raise_on_error
 
 LIB_PATH = os.path.join(_PKG_DIR, "libdcl_dconv.so")
 TILE_P = 128          # DDC_TILE_P
@@ -45,28 +46,13 @@ def lib():
     """The loaded library; raises if it has not been built."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                f"{LIB_PATH} not found. The dilated convolution kernels have no fallback once selected: build the HIP "
-                f"libraries first (python -c 'import __graft_entry__ as g; g.build()' or make -C {CSRC_DIR}).")
-        l = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in SIGNATURES.items():
-            fn = getattr(l, name)
-            fn.argtypes = argtypes
-            fn.restype = ctypes.c_int
-        l.ddc_live_taps.restype = ctypes.c_uint
-        l.ddc_workspace_bytes.restype = ctypes.c_int64
-        l.ddc_packed_bytes.restype = ctypes.c_int64
-        l.ddc_last_error.restype = ctypes.c_char_p
-        l.ddc_last_error.argtypes = []
-        _lib = l
+        _lib = load_library(LIB_PATH, SIGNATURES, "ddc", "dilated convolution kernels",
+                            restypes={"ddc_live_taps": ctypes.c_uint, "ddc_workspace_bytes": _i64, "ddc_packed_bytes": _i64})
     return _lib
 
 
 def check(rc: int, what: str):
-    if rc != 0:
-        msg = lib().ddc_last_error().decode("utf-8", "replace")
-        raise RuntimeError(f"{what} failed (code {rc}): {msg}")
+    raise_on_error(rc, what, lib().ddc_last_error)
 
 
 def supported(n: int, ci: int, co: int, h: int, w: int, d: int) -> bool:

@@ -6,6 +6,7 @@ import ctypes
 import os
 
 from ._lib import CSRC_DIR, _PKG_DIR, ptr, stream_ptr  # noqa: F401  (re-exported for callers of this module)
+from ._lib import load_library, raise_on_error
 
 LIB_PATH = os.path.join(_PKG_DIR, "libdcl_pred.so")
 MAX_C = 256           # DPR_MAX_C
@@ -40,25 +41,12 @@ def lib():
     """The loaded library; raises if it has not been built."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                f"{LIB_PATH} not found. The prediction-map kernels have no fallback once selected: build the HIP "
-                f"libraries first (python -c 'import __graft_entry__ as g; g.build()' or make -C {CSRC_DIR}).")
-        l = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in SIGNATURES.items():
-            fn = getattr(l, name)
-            fn.argtypes = argtypes
-            fn.restype = ctypes.c_int
-        l.dpr_last_error.restype = ctypes.c_char_p
-        l.dpr_last_error.argtypes = []
-        _lib = l
+        _lib = load_library(LIB_PATH, SIGNATURES, "dpr", "prediction-map kernels")
     return _lib
 
 
 def check(rc: int, what: str):
-    if rc != 0:
-        msg = lib().dpr_last_error().decode("utf-8", "replace")
-        raise RuntimeError(f"{what} failed (code {rc}): {msg}")
+    raise_on_error(rc, what, lib().dpr_last_error)
 
 
 def supported(n: int, c: int, h: int, w: int, H: int, W: int, with_rgb: bool = True) -> bool:

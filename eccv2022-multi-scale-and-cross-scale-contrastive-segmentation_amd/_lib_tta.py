@@ -6,6 +6,7 @@ import ctypes
 import os
 
 from ._lib import CSRC_DIR, _PKG_DIR, ptr, stream_ptr  # noqa: F401  (re-exported for callers of this module)
+from ._lib import load_library, raise_on_error
 
 LIB_PATH = os.path.join(_PKG_DIR, "libdcl_tta.so")
 MAX_C = 1024          # DTT_MAX_C
@@ -40,25 +41,12 @@ def lib():
     """The loaded library; raises if it has not been built."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                f"{LIB_PATH} not found. The test-time-augmentation kernels have no fallback once selected: build the HIP "
-                f"libraries first (python -c 'import __graft_entry__ as g; g.build()' or make -C {CSRC_DIR}).")
-        l = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in SIGNATURES.items():
-            fn = getattr(l, name)
-            fn.argtypes = argtypes
-            fn.restype = ctypes.c_int
-        l.dtt_last_error.restype = ctypes.c_char_p
-        l.dtt_last_error.argtypes = []
-        _lib = l
+        _lib = load_library(LIB_PATH, SIGNATURES, "dtt", "test-time-augmentation kernels")
     return _lib
 
 
 def check(rc: int, what: str):
-    if rc != 0:
-        msg = lib().dtt_last_error().decode("utf-8", "replace")
-        raise RuntimeError(f"{what} failed (code {rc}): {msg}")
+    raise_on_error(rc, what, lib().dtt_last_error)
 
 
 def supported(c: int, h: int, w: int, hm: int, wm: int, H: int, W: int) -> bool:

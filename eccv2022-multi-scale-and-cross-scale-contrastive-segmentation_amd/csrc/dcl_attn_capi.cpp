@@ -1,20 +1,8 @@
 // dcl_attn_capi.cpp -- host-only entries of libdcl_attn.so (include/dcl_attn.h): error text, version, shape test, workspace size.
-#include <stdarg.h>
-#include <stdio.h>
-
 #include "dcl_attn_plan.h"
+#include "dcl_error.h"
 
-static thread_local char g_err[512] = "";
-
-void dat_set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-extern "C" const char *dat_last_error(void) { return g_err; }
+DCL_DEFINE_ERROR_TEXT(dat)
 
 extern "C" int dat_version(void) { return 1; }
 

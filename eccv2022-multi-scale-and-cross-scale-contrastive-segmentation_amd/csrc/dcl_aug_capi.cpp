@@ -1,20 +1,8 @@
 // dcl_aug_capi.cpp -- host-only entries of libdcl_aug.so (include/dcl_aug.h): error text, version, plan test, the index-rule exports.
-#include <stdarg.h>
-#include <stdio.h>
-
 #include "dcl_aug_plan.h"
+#include "dcl_error.h"
 
-static thread_local char g_err[512] = "";
-
-void dau_set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-extern "C" const char *dau_last_error(void) { return g_err; }
+DCL_DEFINE_ERROR_TEXT(dau)
 
 extern "C" int dau_version(void) { return 1; }
 

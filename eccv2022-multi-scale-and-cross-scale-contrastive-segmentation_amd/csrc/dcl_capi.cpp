@@ -1,20 +1,8 @@
 // dcl_capi.cpp -- error plumbing and host-only helpers of the C ABI (include/dcl_hip.h).
-#include <stdarg.h>
-#include <stdio.h>
-
 #include "../../include/dcl_hip.h"
+#include "dcl_error.h"
 
-static thread_local char g_err[512] = "";
-
-void dcl_set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-extern "C" const char *dcl_last_error(void) { return g_err; }
+DCL_DEFINE_ERROR_TEXT(dcl)
 
 // Which kernel symbol did the last convolution / weight-gradient entry point of this thread launch?  (The tile and variant
 // are chosen inside the library; bench.py's in-step kernel timer names its rows with this.)  Off unless switched on.

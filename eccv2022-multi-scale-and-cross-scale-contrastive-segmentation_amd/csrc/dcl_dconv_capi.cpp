@@ -1,21 +1,9 @@
 // dcl_dconv_capi.cpp -- host-only entries of libdcl_dconv.so (include/dcl_dconv.h): error text, version, shape test, live taps,
 // slab count, workspace and fragment sizes.
-#include <stdarg.h>
-#include <stdio.h>
-
 #include "dcl_dconv_plan.h"
+#include "dcl_error.h"
 
-static thread_local char g_err[512] = "";
-
-void ddc_set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-extern "C" const char *ddc_last_error(void) { return g_err; }
+DCL_DEFINE_ERROR_TEXT(ddc)
 
 extern "C" int ddc_version(void) { return 1; }
 

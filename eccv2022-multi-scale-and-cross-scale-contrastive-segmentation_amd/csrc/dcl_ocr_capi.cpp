@@ -1,20 +1,8 @@
 // dcl_ocr_capi.cpp -- host-only entries of libdcl_ocr.so (include/dcl_ocr.h): error text, version, shape test, workspace size.
-#include <stdarg.h>
-#include <stdio.h>
-
 #include "dcl_ocr_plan.h"
+#include "dcl_error.h"
 
-static thread_local char g_err[512] = "";
-
-void dco_set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-extern "C" const char *dco_last_error(void) { return g_err; }
+DCL_DEFINE_ERROR_TEXT(dco)
 
 extern "C" int dco_version(void) { return 1; }
 

@@ -1,20 +1,8 @@
 // dcl_pred_capi.cpp -- host-only entries of libdcl_pred.so (include/dcl_pred.h): error text, version, shape tests, the plan exports.
-#include <stdarg.h>
-#include <stdio.h>
-
 #include "dcl_pred_plan.h"
+#include "dcl_error.h"
 
-static thread_local char g_err[512] = "";
-
-void dpr_set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-extern "C" const char *dpr_last_error(void) { return g_err; }
+DCL_DEFINE_ERROR_TEXT(dpr)
 
 extern "C" int dpr_version(void) { return 1; }
 
@@ -31,7 +19,7 @@ extern "C" int dpr_plan_src_index(int in_size, int out_size, int align, int dst,
         dpr_set_error("dpr_plan_src_index: bad arguments");
         return DPR_EINVAL;
     }
-    dpr_src_index(dpr_axis_scale(in_size, out_size, align ? 1 : 0), align ? 1 : 0, dst, in_size, i0, i1, l0, l1);
+    dcl_bilinear_src_index(dcl_bilinear_scale(in_size, out_size, align ? 1 : 0), align ? 1 : 0, dst, in_size, i0, i1, l0, l1);
     return DPR_OK;
 }
 

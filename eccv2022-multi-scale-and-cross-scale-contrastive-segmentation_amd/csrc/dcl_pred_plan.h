@@ -1,17 +1,10 @@
 // dcl_pred_plan.h -- what dcl_pred.hip, dcl_pred_capi.cpp and the host tests share: the shape tests, the run / word-store decision
-// and the bilinear source index.  Host-compilable: plain functions, no HIP (DPR_HD is empty unless a HIP compiler reads this, where
-// it lets the kernels call the same source-index code).
+// and (dcl_bilinear.h) the bilinear source index.  Host-compilable: plain functions, no HIP.
 #pragma once
-#include <math.h>
 #include <stdint.h>
 
 #include "../../include/dcl_pred.h"
-
-#ifdef __HIPCC__
-#define DPR_HD __host__ __device__
-#else
-#define DPR_HD
-#endif
+#include "dcl_bilinear.h"
 
 void dpr_set_error(const char *fmt, ...);
 
@@ -48,25 +41,4 @@ static inline int dpr_class_split(int64_t items, int N, int C)
     while (split < 8 && blocks * split < 2048 && C / (2 * split) >= 8)
         split *= 2;
     return split;
-}
-
-// ATen's area_pixel_compute_scale (f32)
-DPR_HD static inline float dpr_axis_scale(int in_size, int out_size, int align)
-{
-    if (align)
-        return out_size > 1 ? (float)(in_size - 1) / (float)(out_size - 1) : 0.f;
-    return (float)in_size / (float)out_size;
-}
-
-// ATen's area_pixel_compute_source_index + the index pair and weights of upsample_bilinear2d (as csrc/dcl_tta_plan.h dtt_src_index)
-DPR_HD static inline void dpr_src_index(float scale, int align, int dst, int in_size, int *i0, int *i1, float *l0, float *l1)
-{
-    const float s = align ? scale * (float)dst : fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.f);
-    int a = (int)s;
-    if (a > in_size - 1)
-        a = in_size - 1;
-    *i0 = a;
-    *i1 = a + (a < in_size - 1 ? 1 : 0);
-    *l1 = s - (float)a;
-    *l0 = 1.f - *l1;
 }

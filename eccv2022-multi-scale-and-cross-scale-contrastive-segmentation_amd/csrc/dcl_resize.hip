@@ -4,10 +4,8 @@
 // step at BASELINE config 2.  PyTorch's kernel reaches ~270 GB/s there (one thread per output element,
 // scalar stores) and its backward uses float atomics; this one writes 16 B per lane and gathers.
 //
-// Index arithmetic restates ATen's (UpSample.h: area_pixel_compute_scale / _source_index, f32):
-//   align_corners: scale = (in-1)/(out-1) (0 if out == 1), src = scale * dst
-//   otherwise    : scale = in/out,                         src = max(scale * (dst + 0.5) - 0.5, 0)
-//   i0 = (int)src, i1 = i0 + (i0 < in-1), l1 = src - i0, l0 = 1 - l1
+// Index arithmetic: dcl_bilinear.h (ATen's, f32), shared with every other bilinear kernel of the project.
+#include "dcl_bilinear.h"
 #include "dcl_common.h"
 
 namespace {
@@ -17,16 +15,18 @@ struct Axis {
     int align;
 };
 
-__device__ __forceinline__ void src_index(const Axis a, int dst, int in_size, int &i0, int &i1, float &l0,
-                                          float &l1)
+// dcl_bilinear.h on an Axis.  The Axis goes by value, as it reaches the kernels: its two fields are then read together, once.
+__host__ __device__ __forceinline__ void bl_index(const Axis a, int dst, int in_size, int &i0, int &i1, float &l0, float &l1)
 {
-    float s = a.align ? a.scale * (float)dst : fmaxf(a.scale * ((float)dst + 0.5f) - 0.5f, 0.f);
-    i0 = (int)s;
-    if (i0 > in_size - 1)
-        i0 = in_size - 1;
-    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-    l1 = s - (float)i0;
-    l0 = 1.f - l1;
+    dcl_bilinear_src_index(a.scale, a.align, dst, in_size, &i0, &i1, &l0, &l1);
+}
+__host__ __device__ __forceinline__ float bl_weight(const Axis a, int o, int in_size, int i)
+{
+    return dcl_bilinear_weight(a.scale, a.align, o, in_size, i);
+}
+__host__ __device__ __forceinline__ void bl_range(const Axis a, int i, int in_size, int out_size, int &lo, int &hi)
+{
+    dcl_bilinear_out_range(a.scale, a.align, i, in_size, out_size, &lo, &hi);
 }
 
 // The high-resolution tensor may be a channel slice [c0, c0 + C) of a wider [N, ctot, H, W] tensor (the concatenation
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void k_upsample_fwd(const float *__restrict__ 
     const size_t plane = row / H;
     int y0, y1;
     float ly0, ly1;
-    src_index(ay, oy, h, y0, y1, ly0, ly1);
+    bl_index(ay, oy, h, y0, y1, ly0, ly1);
     const float *r0 = x + (plane * h + y0) * (size_t)w;
     const float *r1 = x + (plane * h + y1) * (size_t)w;
     float *out = y + (wide_plane(sl, plane) * H + oy) * (size_t)W;
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256) void k_upsample_fwd(const float *__restrict__ 
             if (ox < W) {
                 int x0, x1;
                 float lx0, lx1;
-                src_index(ax, ox, w, x0, x1, lx0, lx1);
+                bl_index(ax, ox, w, x0, x1, lx0, lx1);
                 v[k] = ly0 * (lx0 * r0[x0] + lx1 * r0[x1]) + ly1 * (lx0 * r1[x0] + lx1 * r1[x1]);
             } else {
                 v[k] = 0.f;
@@ -90,38 +90,6 @@ __global__ __launch_bounds__(256) void k_upsample_fwd(const float *__restrict__ 
     }
 }
 
-// weight of input index `i` in output index `o` along one axis
-__device__ __forceinline__ float axis_weight(const Axis a, int o, int in_size, int i)
-{
-    int i0, i1;
-    float l0, l1;
-    src_index(a, o, in_size, i0, i1, l0, l1);
-    return (i0 == i ? l0 : 0.f) + (i1 == i ? l1 : 0.f);
-}
-
-// candidate output range touching input index i (conservative; weights decide)
-__host__ __device__ __forceinline__ void out_range(const Axis a, int i, int in_size, int out_size, int &lo, int &hi)
-{
-    // src(o) is non-decreasing in o; input i is touched when src(o) in (i-1, i+1)
-    const float inv = a.scale > 0.f ? 1.f / a.scale : 0.f;
-    float flo, fhi;
-    if (a.align) {
-        flo = ((float)i - 1.f) * inv;
-        fhi = ((float)i + 1.f) * inv;
-    } else {
-        flo = ((float)i - 1.f + 0.5f) * inv - 0.5f;
-        fhi = ((float)i + 1.f + 0.5f) * inv - 0.5f;
-    }
-    lo = (int)floorf(flo) - 1;
-    hi = (int)ceilf(fhi) + 1;
-    if (a.scale <= 0.f) {
-        lo = 0;
-        hi = out_size - 1;
-    }
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > out_size - 1 ? out_size - 1 : hi;
-}
-
 // one thread per input element: dx[n,c,iy,ix] = sum_{oy,ox} wy(iy,oy) * wx(ix,ox) * dy[n,c,oy,ox]
 __global__ __launch_bounds__(256) void k_upsample_bwd(const float *__restrict__ dy, int h, int w, int H,
                                                      int W, Axis ay, Axis ax, size_t total,
@@ -135,8 +103,8 @@ __global__ __launch_bounds__(256) void k_upsample_bwd(const float *__restrict__ 
     const int iy = (int)(t % h);
     const size_t plane = t / h;
     int oy_lo, oy_hi, ox_lo, ox_hi;
-    out_range(ay, iy, h, H, oy_lo, oy_hi);
-    out_range(ax, ix, w, W, ox_lo, ox_hi);
+    bl_range(ay, iy, h, H, oy_lo, oy_hi);
+    bl_range(ax, ix, w, W, ox_lo, ox_hi);
     const float *g = dy + wide_plane(sl, plane) * (size_t)H * W;
     // separable: the x-weights of this input column are evaluated once, not once per output row
     constexpr int MAXC = 16;
@@ -145,11 +113,11 @@ __global__ __launch_bounds__(256) void k_upsample_bwd(const float *__restrict__ 
     if (nx <= MAXC) {
 #pragma unroll
         for (int k = 0; k < MAXC; ++k)
-            wxs[k] = k < nx ? axis_weight(ax, ox_lo + k, w, ix) : 0.f;
+            wxs[k] = k < nx ? bl_weight(ax, ox_lo + k, w, ix) : 0.f;
     }
     float acc = 0.f;
     for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-        const float wy = axis_weight(ay, oy, h, iy);
+        const float wy = bl_weight(ay, oy, h, iy);
         if (wy == 0.f)
             continue;
         float rowacc = 0.f;
@@ -161,7 +129,7 @@ __global__ __launch_bounds__(256) void k_upsample_bwd(const float *__restrict__ 
                     rowacc += wxs[k] * gr[k];
         } else {                                   // down-scaling or huge factors: generic path
             for (int k = 0; k < nx; ++k)
-                rowacc += axis_weight(ax, ox_lo + k, w, ix) * gr[k];
+                rowacc += bl_weight(ax, ox_lo + k, w, ix) * gr[k];
         }
         acc += wy * rowacc;
     }
@@ -185,12 +153,12 @@ __global__ __launch_bounds__(256) void k_upsample_bwd_rows(const float *__restri
     const int iy = row % h;
     const size_t plane = row / h;
     int oy_lo, oy_hi;
-    out_range(ay, iy, h, H, oy_lo, oy_hi);
+    bl_range(ay, iy, h, H, oy_lo, oy_hi);
     const float *g = dy + wide_plane(sl, plane) * (size_t)H * W;
     for (int ox4 = threadIdx.x * 4; ox4 < W; ox4 += blockDim.x * 4) {
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-            const float wy = axis_weight(ay, oy, h, iy);          // wave-uniform
+            const float wy = bl_weight(ay, oy, h, iy);          // wave-uniform
             if (wy == 0.f)
                 continue;
             const f32x4 v = *(const f32x4 *)(g + (size_t)oy * W + ox4);
@@ -204,10 +172,10 @@ __global__ __launch_bounds__(256) void k_upsample_bwd_rows(const float *__restri
     __syncthreads();
     for (int ix = threadIdx.x; ix < w; ix += blockDim.x) {
         int ox_lo, ox_hi;
-        out_range(ax, ix, w, W, ox_lo, ox_hi);
+        bl_range(ax, ix, w, W, ox_lo, ox_hi);
         float acc = 0.f;
         for (int ox = ox_lo; ox <= ox_hi; ++ox)
-            acc += axis_weight(ax, ox, w, ix) * tmp[ox];
+            acc += bl_weight(ax, ox, w, ix) * tmp[ox];
         dx[(size_t)row * w + ix] = acc;
     }
 }
@@ -216,10 +184,7 @@ Axis make_axis(int in_size, int out_size, int align)
 {
     Axis a;
     a.align = align;
-    if (align)
-        a.scale = out_size > 1 ? (float)(in_size - 1) / (float)(out_size - 1) : 0.f;
-    else
-        a.scale = (float)in_size / (float)out_size;
+    a.scale = dcl_bilinear_scale(in_size, out_size, align);
     return a;
 }
 
@@ -346,10 +311,10 @@ __global__ __launch_bounds__(TAP_TW) void k_tapup_fwd(TapSrc s0, TapSrc s1, int 
         const TapSrc s = si == 0 ? s0 : s1;
         int ra, rb, ca, cb, d0, d1;
         float f0, f1;
-        src_index(s.ay, max(Y0 - 1, 0), s.h, ra, d1, f0, f1);
-        src_index(s.ay, min(Y0 + TAP_RC, H - 1), s.h, d0, rb, f0, f1);
-        src_index(s.ax, max(X0 - 1, 0), s.w, ca, d1, f0, f1);
-        src_index(s.ax, min(X0 + TAP_TW, W - 1), s.w, d0, cb, f0, f1);
+        bl_index(s.ay, max(Y0 - 1, 0), s.h, ra, d1, f0, f1);
+        bl_index(s.ay, min(Y0 + TAP_RC, H - 1), s.h, d0, rb, f0, f1);
+        bl_index(s.ax, max(X0 - 1, 0), s.w, ca, d1, f0, f1);
+        bl_index(s.ax, min(X0 + TAP_TW, W - 1), s.w, d0, cb, f0, f1);
         const int nr = rb - ra + 1, nc = cb - ca + 1;           // <= s.wr, s.wc - 1 (host-side bound)
         const float *zp = s.z + (size_t)n * s.sn + (size_t)co * s.sc;
         const size_t tapstride = (size_t)Co * s.sc;
@@ -385,7 +350,7 @@ __global__ __launch_bounds__(TAP_TW) void k_tapup_fwd(TapSrc s0, TapSrc s1, int 
             int r0 = ra, r1 = ra;
             float l0 = 0.f, l1 = 0.f;
             if (Ys >= 0 && Ys < H)
-                src_index(s.ay, Ys, s.h, r0, r1, l0, l1);
+                bl_index(s.ay, Ys, s.h, r0, r1, l0, l1);
             float *e = rtab + (si * (TAP_RC + 2) + j) * 4;
             e[0] = __int_as_float((r0 - ra) * s.wc);
             e[1] = __int_as_float((r1 - ra) * s.wc);
@@ -398,7 +363,7 @@ __global__ __launch_bounds__(TAP_TW) void k_tapup_fwd(TapSrc s0, TapSrc s1, int 
             int c0 = ca, c1 = ca;
             float l0 = 0.f, l1 = 0.f;
             if (Xs >= 0 && Xs < W && X < W)
-                src_index(s.ax, Xs, s.w, c0, c1, l0, l1);
+                bl_index(s.ax, Xs, s.w, c0, c1, l0, l1);
             cix[si][kx] = c0 - ca;
             cw0[si][kx] = l0;
             cw1[si][kx] = (c1 == c0) ? 0.f : l1;                // right neighbour = c0 + 1 or (border) weightless
@@ -519,22 +484,22 @@ __global__ __launch_bounds__(256) void k_tapup_bwd(const float *__restrict__ dy,
     const int n = plane / Co, co = plane - n * Co;
     const int r_a = tile * trl, r_b = min(r_a + trl, h) - 1;
     int lo, hi, d0, d1;
-    out_range(ay, r_a, h, H, lo, d1);
-    out_range(ay, r_b, h, H, d0, hi);
+    bl_range(ay, r_a, h, H, lo, d1);
+    bl_range(ay, r_b, h, H, d0, hi);
     const int Ya = max(lo - 1, 0), Yb = min(hi + 1, H - 1);       // rows of dy whose shifted coordinate may touch the tile
     const int nrows = min(Yb - Ya + 1, gr);
     const int t = threadIdx.x;
     for (int e = t; e < nrows * 3 * TAP_TRL; e += 256) {
         const int rr = e % TAP_TRL, ky = (e / TAP_TRL) % 3, j = e / (3 * TAP_TRL);
         const int Ys = Ya + j + ky - 1;
-        wt[e] = (rr <= r_b - r_a && Ys >= 0 && Ys < H) ? axis_weight(ay, Ys, h, r_a + rr) : 0.f;
+        wt[e] = (rr <= r_b - r_a && Ys >= 0 && Ys < H) ? bl_weight(ay, Ys, h, r_a + rr) : 0.f;
     }
     for (int c = t; c < w; c += 256) {
         int xs_lo, xs_hi;
-        out_range(ax, c, w, W, xs_lo, xs_hi);
+        bl_range(ax, c, w, W, xs_lo, xs_hi);
         xlo[c] = xs_lo;
         for (int k = 0; k < kxn; ++k)
-            wxt[c * kxn + k] = (xs_lo + k <= xs_hi) ? axis_weight(ax, xs_lo + k, w, c) : 0.f;
+            wxt[c * kxn + k] = (xs_lo + k <= xs_hi) ? bl_weight(ax, xs_lo + k, w, c) : 0.f;
     }
     __syncthreads();
     const float *g = dy + ((size_t)plane * H + Ya) * W;
@@ -599,7 +564,7 @@ __global__ __launch_bounds__(256) void k_tapup_bwd_w(const float *__restrict__ d
                                                     long long sn, long long sc, int planes, int ppw, float *__restrict__ amax)
 {
     float am = 0.f;
-    // Round 4: a workgroup takes `ppw` consecutive planes of its row tile (the weight tables -- axis_weight has a division per
+    // Round 4: a workgroup takes `ppw` consecutive planes of its row tile (the weight tables -- bl_weight has a division per
     // entry -- are built once for all of them), and the vertical pass reads dy as float4s with every row of a footprint in
     // flight: one item = (low-resolution row, four columns), up to 8 x 16 bytes per thread outstanding.  Before, a thread had
     // four 4-byte loads in flight and half the threads idled on a 128-column map: 3.5 ms per launch on 16 x 512 x 128 x 128 where
@@ -619,12 +584,12 @@ __global__ __launch_bounds__(256) void k_tapup_bwd_w(const float *__restrict__ d
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         int lo = 0, hi = 0;
         if (rr < nr) {
-            out_range(ay, r_a + rr, h, H, lo, hi);
+            bl_range(ay, r_a + rr, h, H, lo, hi);
             const int Y = lo - 1 + j;
             if (Y >= 0 && Y < H && Y <= hi + 1) {
-                v.x = (Y - 1 >= 0) ? axis_weight(ay, Y - 1, h, r_a + rr) : 0.f;
-                v.y = axis_weight(ay, Y, h, r_a + rr);
-                v.z = (Y + 1 < H) ? axis_weight(ay, Y + 1, h, r_a + rr) : 0.f;
+                v.x = (Y - 1 >= 0) ? bl_weight(ay, Y - 1, h, r_a + rr) : 0.f;
+                v.y = bl_weight(ay, Y, h, r_a + rr);
+                v.z = (Y + 1 < H) ? bl_weight(ay, Y + 1, h, r_a + rr) : 0.f;
             }
         }
         wt[e] = v;
@@ -633,7 +598,7 @@ __global__ __launch_bounds__(256) void k_tapup_bwd_w(const float *__restrict__ d
     }
     for (int c = t; c < w; c += 256) {
         int xs_lo, xs_hi;
-        out_range(ax, c, w, W, xs_lo, xs_hi);
+        bl_range(ax, c, w, W, xs_lo, xs_hi);
         a4s[c] = (xs_lo - 1 + PADL) & ~3;
     }
     for (int e = t; e < 3 * TAP_TRL * (WP - W); e += 256) {                 // zero pads of the V rows
@@ -645,8 +610,8 @@ __global__ __launch_bounds__(256) void k_tapup_bwd_w(const float *__restrict__ d
         const int c = e / (TS * 4), m = e - c * (TS * 4);
         const int Xs = a4s[c] - PADL + m - 1;
         int xs_lo, xs_hi;
-        out_range(ax, c, w, W, xs_lo, xs_hi);
-        ((float *)wf)[e] = (m < 4 * NW4 + 2 && Xs >= xs_lo && Xs <= xs_hi) ? axis_weight(ax, Xs, w, c) : 0.f;
+        bl_range(ax, c, w, W, xs_lo, xs_hi);
+        ((float *)wf)[e] = (m < 4 * NW4 + 2 && Xs >= xs_lo && Xs <= xs_hi) ? bl_weight(ax, Xs, w, c) : 0.f;
     }
     for (int pp = 0; pp < ppw && plane0 + pp < planes; ++pp) {
     const int plane = plane0 + pp;
@@ -765,7 +730,7 @@ int tap_window(int in_size, int out_size, int n_out)
     return wdw > in_size ? in_size : (wdw < 2 ? 2 : wdw);
 }
 
-// output coordinates whose interpolation can touch one input index (bound of out_range's span), + margin
+// output coordinates whose interpolation can touch one input index (bound of bl_range's span), + margin
 int tap_footprint(int in_size, int out_size)
 {
     const double inv = in_size > 0 ? (double)out_size / (double)in_size : 1.0;
@@ -911,17 +876,17 @@ static int tapup_bwd_impl(const float *dy, int N, int Co, int H, int W, int h, i
     const long long sn = channel_major ? (long long)h * w : (long long)9 * Co * h * w;
     const long long sc = channel_major ? (long long)N * h * w : (long long)h * w;
     // second form: 4 low-resolution rows per tile, a column window of NW4 float4s
-    // exact spans of out_range() over the rows / columns (+ 1: host and device may round a quotient differently);
+    // exact spans of bl_range() over the rows / columns (+ 1: host and device may round a quotient differently);
     // tap_footprint()'s 2 s + 6 is too small for align_corners on few source pixels (3 -> 24: s = 11.5, not 8)
     int span_r = 1, span_c = 1;
     for (int r = 0; r < h; ++r) {
         int lo, hi;
-        out_range(ay, r, h, H, lo, hi);
+        bl_range(ay, r, h, H, lo, hi);
         span_r = hi - lo + 1 > span_r ? hi - lo + 1 : span_r;
     }
     for (int c = 0; c < w; ++c) {
         int lo, hi;
-        out_range(ax, c, w, W, lo, hi);
+        bl_range(ax, c, w, W, lo, hi);
         span_c = hi - lo + 1 > span_c ? hi - lo + 1 : span_c;
     }
     const int nw4 = (span_c + 1 + 5 + 3) / 4, FR = span_r + 1 + 2, PADL = 4;

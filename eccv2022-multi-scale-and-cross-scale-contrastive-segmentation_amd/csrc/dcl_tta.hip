@@ -38,14 +38,14 @@ Axis make_axis(int in_size, int out_size, int align)
     Axis a;
     a.align = align ? 1 : 0;
     a.in = in_size;
-    a.scale = dtt_axis_scale(in_size, out_size, a.align);
+    a.scale = dcl_bilinear_scale(in_size, out_size, a.align);
     return a;
 }
 
 __device__ __forceinline__ Tap tap(const Axis a, int dst)
 {
     Tap t;
-    dtt_src_index(a.scale, a.align, dst, a.in, &t.i0, &t.i1, &t.l0, &t.l1);
+    dcl_bilinear_src_index(a.scale, a.align, dst, a.in, &t.i0, &t.i1, &t.l0, &t.l1);
     return t;
 }
 

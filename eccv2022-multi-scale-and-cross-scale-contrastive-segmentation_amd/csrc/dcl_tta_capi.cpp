@@ -1,20 +1,8 @@
 // dcl_tta_capi.cpp -- host-only entries of libdcl_tta.so (include/dcl_tta.h): error text, version, shape test, the plan exports.
-#include <stdarg.h>
-#include <stdio.h>
-
 #include "dcl_tta_plan.h"
+#include "dcl_error.h"
 
-static thread_local char g_err[512] = "";
-
-void dtt_set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-extern "C" const char *dtt_last_error(void) { return g_err; }
+DCL_DEFINE_ERROR_TEXT(dtt)
 
 extern "C" int dtt_version(void) { return 1; }
 
@@ -50,6 +38,6 @@ extern "C" int dtt_plan_src_index(int in_size, int out_size, int align, int dst,
         dtt_set_error("dtt_plan_src_index: bad arguments");
         return DTT_EINVAL;
     }
-    dtt_src_index(dtt_axis_scale(in_size, out_size, align ? 1 : 0), align ? 1 : 0, dst, in_size, i0, i1, l0, l1);
+    dcl_bilinear_src_index(dcl_bilinear_scale(in_size, out_size, align ? 1 : 0), align ? 1 : 0, dst, in_size, i0, i1, l0, l1);
     return DTT_OK;
 }

@@ -1,17 +1,12 @@
 // dcl_tta_plan.h -- what dcl_tta.hip, dcl_tta_capi.cpp and the host tests share: the shape test, the Cityscapes image-size rule,
-// the sliding-window grid with its separable counts, and the bilinear source index.  Host-compilable: plain functions, no HIP
-// (DTT_HD is empty unless a HIP compiler reads this, where it lets the kernels call the same source-index code).
+// the sliding-window grid with its separable counts, and (dcl_bilinear.h) the bilinear source index.  Host-compilable: plain
+// functions, no HIP.
 #pragma once
 #include <math.h>
 #include <stdint.h>
 
 #include "../../include/dcl_tta.h"
-
-#ifdef __HIPCC__
-#define DTT_HD __host__ __device__
-#else
-#define DTT_HD
-#endif
+#include "dcl_bilinear.h"
 
 void dtt_set_error(const char *fmt, ...);
 
@@ -66,25 +61,4 @@ static inline int dtt_window_counts(int n, int crop, int stride, int32_t *cnt)
             cnt[i] += 1;
     }
     return count;
-}
-
-// ATen's area_pixel_compute_scale (f32)
-DTT_HD static inline float dtt_axis_scale(int in_size, int out_size, int align)
-{
-    if (align)
-        return out_size > 1 ? (float)(in_size - 1) / (float)(out_size - 1) : 0.f;
-    return (float)in_size / (float)out_size;
-}
-
-// ATen's area_pixel_compute_source_index + the index pair and weights of upsample_bilinear2d (as csrc/dcl_resize.hip src_index)
-DTT_HD static inline void dtt_src_index(float scale, int align, int dst, int in_size, int *i0, int *i1, float *l0, float *l1)
-{
-    const float s = align ? scale * (float)dst : fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.f);
-    int a = (int)s;
-    if (a > in_size - 1)
-        a = in_size - 1;
-    *i0 = a;
-    *i1 = a + (a < in_size - 1 ? 1 : 0);
-    *l1 = s - (float)a;
-    *l0 = 1.f - *l1;
 }

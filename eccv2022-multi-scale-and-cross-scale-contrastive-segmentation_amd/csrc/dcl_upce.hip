@@ -6,7 +6,7 @@
 // unfused chain writes / reads that tensor (and its gradient) ~9 times per step.  Here the full-resolution logits exist
 // only in registers:
 //   forward : one workgroup per OUTPUT row; the two source rows of every class are staged in LDS; each thread owns 4
-//             consecutive pixels, interpolates the class logits on the fly (ATen's index arithmetic, dcl_resize.hip),
+//             consecutive pixels, interpolates the class logits on the fly (ATen's index arithmetic, dcl_bilinear.h),
 //             online log-sum-exp, picks the target logit, emits  lse [N,H,W] (saved for the backward), the arg-max
 //             class (uint8 map: the confusion matrix needs nothing else) and per-row partial sums {sum w_t (lse - v_t),
 //             sum w_t}: loss = sum / sum, PyTorch's weighted-mean reduction (ignored pixels in neither);
@@ -18,6 +18,7 @@
 // HBM-bound: reads z (30 MB), labels and lse; writes lse / prediction / dz.
 #include <type_traits>
 
+#include "dcl_bilinear.h"
 #include "dcl_common.h"
 
 namespace {
@@ -27,54 +28,25 @@ struct Axis {
     int align;
 };
 
-__device__ __forceinline__ void src_index(const Axis a, int dst, int in_size, int &i0, int &i1, float &l0, float &l1)
+// dcl_bilinear.h on an Axis.  The Axis goes by value, as it reaches the kernels: its two fields are then read together, once.
+__device__ __forceinline__ void bl_index(const Axis a, int dst, int in_size, int &i0, int &i1, float &l0, float &l1)
 {
-    float s = a.align ? a.scale * (float)dst : fmaxf(a.scale * ((float)dst + 0.5f) - 0.5f, 0.f);
-    i0 = (int)s;
-    if (i0 > in_size - 1)
-        i0 = in_size - 1;
-    i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-    l1 = s - (float)i0;
-    l0 = 1.f - l1;
+    dcl_bilinear_src_index(a.scale, a.align, dst, in_size, &i0, &i1, &l0, &l1);
 }
-
-__device__ __forceinline__ float axis_weight(const Axis a, int o, int in_size, int i)
+__device__ __forceinline__ float bl_weight(const Axis a, int o, int in_size, int i)
 {
-    int i0, i1;
-    float l0, l1;
-    src_index(a, o, in_size, i0, i1, l0, l1);
-    return (i0 == i ? l0 : 0.f) + (i1 == i ? l1 : 0.f);
+    return dcl_bilinear_weight(a.scale, a.align, o, in_size, i);
 }
-
-__device__ __forceinline__ void out_range(const Axis a, int i, int in_size, int out_size, int &lo, int &hi)
+__device__ __forceinline__ void bl_range(const Axis a, int i, int in_size, int out_size, int &lo, int &hi)
 {
-    const float inv = a.scale > 0.f ? 1.f / a.scale : 0.f;
-    float flo, fhi;
-    if (a.align) {
-        flo = ((float)i - 1.f) * inv;
-        fhi = ((float)i + 1.f) * inv;
-    } else {
-        flo = ((float)i - 1.f + 0.5f) * inv - 0.5f;
-        fhi = ((float)i + 1.f + 0.5f) * inv - 0.5f;
-    }
-    lo = (int)floorf(flo) - 1;
-    hi = (int)ceilf(fhi) + 1;
-    if (a.scale <= 0.f) {
-        lo = 0;
-        hi = out_size - 1;
-    }
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > out_size - 1 ? out_size - 1 : hi;
+    dcl_bilinear_out_range(a.scale, a.align, i, in_size, out_size, &lo, &hi);
 }
 
 Axis make_axis(int in_size, int out_size, int align)
 {
     Axis a;
     a.align = align;
-    if (align)
-        a.scale = out_size > 1 ? (float)(in_size - 1) / (float)(out_size - 1) : 0.f;
-    else
-        a.scale = (float)in_size / (float)out_size;
+    a.scale = dcl_bilinear_scale(in_size, out_size, align);
     return a;
 }
 
@@ -117,7 +89,7 @@ __global__ __launch_bounds__(256) void k_upce_fwd(UpceArgs a)
     const int oy = row % a.H, n = row / a.H;
     int y0, y1;
     float ly0, ly1;
-    src_index(a.ay, oy, a.h, y0, y1, ly0, ly1);
+    bl_index(a.ay, oy, a.h, y0, y1, ly0, ly1);
     const size_t plane = (size_t)a.h * a.w;
     float num = 0.f, den = 0.f;
     for (int trip = 0; trip * 256 * PIX < a.W; ++trip) {            // uniform trip count: barriers inside
@@ -128,7 +100,7 @@ __global__ __launch_bounds__(256) void k_upce_fwd(UpceArgs a)
 #pragma unroll
         for (int k = 0; k < PIX; ++k) {
             const int ox = min(px0 + k, a.W - 1);
-            src_index(a.ax, ox, a.w, x0[k], x1[k], lx0[k], lx1[k]);
+            bl_index(a.ax, ox, a.w, x0[k], x1[k], lx0[k], lx1[k]);
             const long long t = px0 + k < a.W ? a.target[(size_t)row * a.W + ox] : (long long)a.ignore;
             tgt[k] = (t < 0 || t > 0x7fffffff) ? -1 : (int)t;
             m[k] = -INFINITY;
@@ -248,7 +220,7 @@ __global__ __launch_bounds__(256) void k_upce_bwd(UpceArgs a)
     const int iy = row % a.h, n = row / a.h;
     const size_t plane = (size_t)a.h * a.w;
     int oy_lo, oy_hi;
-    out_range(a.ay, iy, a.h, a.H, oy_lo, oy_hi);
+    bl_range(a.ay, iy, a.h, a.H, oy_lo, oy_hi);
     const float gs = a.gscale[0];
     const int ya = max(iy - 1, 0);                  // staged rows ya .. ya + 2 (clamped to the image)
     // per output row of the footprint: {wy, weights of the three staged rows in its interpolation, times log2 e} --
@@ -258,9 +230,9 @@ __global__ __launch_bounds__(256) void k_upce_bwd(UpceArgs a)
         const int oy = oy_lo + j;
         int y0, y1;
         float ly0, ly1;
-        src_index(a.ay, oy, a.h, y0, y1, ly0, ly1);
+        bl_index(a.ay, oy, a.h, y0, y1, ly0, ly1);
         const int r0 = y0 - ya, r1 = y1 - ya;        // both in 0 .. 2 for a row with a non-zero weight
-        rowtab[j][0] = axis_weight(a.ay, oy, a.h, iy);
+        rowtab[j][0] = bl_weight(a.ay, oy, a.h, iy);
 #pragma unroll
         for (int r = 0; r < 3; ++r)
             rowtab[j][1 + r] = ((r0 == r ? ly0 : 0.f) + (r1 == r ? ly1 : 0.f)) * 1.44269502f;
@@ -286,7 +258,7 @@ __global__ __launch_bounds__(256) void k_upce_bwd(UpceArgs a)
         for (int ox = threadIdx.x; ox < a.W; ox += 256) {
             int x0, x1;
             float lx0, lx1;
-            src_index(a.ax, ox, a.w, x0, x1, lx0, lx1);
+            bl_index(a.ax, ox, a.w, x0, x1, lx0, lx1);
             auto block = [&](auto ubt, const int cb) {
                 constexpr int UB = decltype(ubt)::value;
                 float hl[UB][3], acc[UB];
@@ -336,14 +308,14 @@ __global__ __launch_bounds__(256) void k_upce_bwd(UpceArgs a)
         // column and serve every class of the chunk; wider footprints -- scale factors above 4 -- recompute them)
         for (int ix = threadIdx.x & 63; ix < a.w; ix += 64) {
             int ox_lo, ox_hi;
-            out_range(a.ax, ix, a.w, a.W, ox_lo, ox_hi);
+            bl_range(a.ax, ix, a.w, a.W, ox_lo, ox_hi);
             const int cnt = ox_hi - ox_lo + 1;
             float *dst = a.dz + ((size_t)n * a.C + c0) * plane + (size_t)iy * a.w + ix;
             if (cnt <= 12) {
                 float wx[12];
 #pragma unroll
                 for (int j = 0; j < 12; ++j)
-                    wx[j] = j < cnt ? axis_weight(a.ax, ox_lo + j, a.w, ix) : 0.f;
+                    wx[j] = j < cnt ? bl_weight(a.ax, ox_lo + j, a.w, ix) : 0.f;
                 for (int c = threadIdx.x >> 6; c < nc; c += 4) {
                     const float *tr = tile + c * a.W + ox_lo;
                     float acc = 0.f;
@@ -356,7 +328,7 @@ __global__ __launch_bounds__(256) void k_upce_bwd(UpceArgs a)
                 for (int c = threadIdx.x >> 6; c < nc; c += 4) {
                     float acc = 0.f;
                     for (int ox = ox_lo; ox <= ox_hi; ++ox)
-                        acc += axis_weight(a.ax, ox, a.w, ix) * tile[c * a.W + ox];
+                        acc += bl_weight(a.ax, ox, a.w, ix) * tile[c * a.W + ox];
                     dst[(size_t)c * plane] = acc;
                 }
             }

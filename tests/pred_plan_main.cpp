@@ -41,21 +41,21 @@ static int walk(int C, int h, int w, int H, int W, int align, size_t shift)
     CHECK(runs * DPR_RUN >= W && (runs - 1) * DPR_RUN < W);
     if (shift % 4)
         CHECK(!v1 && !v3);
-    const float sy = dpr_axis_scale(h, H, align), sx = dpr_axis_scale(w, W, align);
+    const float sy = dcl_bilinear_scale(h, H, align), sx = dcl_bilinear_scale(w, W, align);
     for (int64_t item = 0; item < (int64_t)H * runs; ++item) {
         const int Y = (int)(item / runs), X0 = (int)(item - (int64_t)Y * runs) * DPR_RUN;
         const int n = W - X0 < DPR_RUN ? W - X0 : DPR_RUN;
         CHECK(n >= 1);
         int y0, y1;
         float ly0, ly1;
-        dpr_src_index(sy, align, Y, h, &y0, &y1, &ly0, &ly1);
+        dcl_bilinear_src_index(sy, align, Y, h, &y0, &y1, &ly0, &ly1);
         CHECK(0 <= y0 && y0 <= y1 && y1 < h && y1 - y0 <= 1 && ly0 >= 0.f && ly1 >= 0.f && ly0 <= 1.f && ly1 <= 1.f);
         int arg[DPR_RUN];
         for (int k = 0; k < DPR_RUN; ++k) {
             const int X = X0 + k < W - 1 ? X0 + k : W - 1;
             int x0, x1;
             float lx0, lx1;
-            dpr_src_index(sx, align, X, w, &x0, &x1, &lx0, &lx1);
+            dcl_bilinear_src_index(sx, align, X, w, &x0, &x1, &lx0, &lx1);
             CHECK(0 <= x0 && x0 <= x1 && x1 < w && x1 - x0 <= 1 && lx0 >= 0.f && lx1 >= 0.f && lx0 <= 1.f && lx1 <= 1.f);
             float best = 0.f;
             arg[k] = 0;
@@ -109,7 +109,7 @@ int main(int argc, char **argv)
     while (fscanf(f, "%d %d %d %d %d %d %x %x", &in, &out, &align, &dst, &i0, &i1, &b0, &b1) == 8) {
         int g0, g1;
         float l0, l1;
-        dpr_src_index(dpr_axis_scale(in, out, align), align, dst, in, &g0, &g1, &l0, &l1);
+        dcl_bilinear_src_index(dcl_bilinear_scale(in, out, align), align, dst, in, &g0, &g1, &l0, &l1);
         unsigned c0, c1;
         memcpy(&c0, &l0, 4);
         memcpy(&c1, &l1, 4);

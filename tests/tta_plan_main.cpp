@@ -75,13 +75,13 @@ int main()
     for (int in = 1; in <= 40; in += 3)
         for (int out = 1; out <= 90; out += 7)
             for (int align = 0; align < 2; ++align) {
-                const float scale = dtt_axis_scale(in, out, align);
+                const float scale = dcl_bilinear_scale(in, out, align);
                 std::vector<float> row(in, 1.f);
                 int last = 0;
                 for (int dst = 0; dst < out; ++dst) {
                     int i0, i1;
                     float l0, l1;
-                    dtt_src_index(scale, align, dst, in, &i0, &i1, &l0, &l1);
+                    dcl_bilinear_src_index(scale, align, dst, in, &i0, &i1, &l0, &l1);
                     CHECK(0 <= i0 && i0 <= i1 && i1 <= in - 1 && i1 - i0 <= 1 && i0 >= last);
                     CHECK(l1 >= 0.f && l0 + l1 > 0.999f && l0 + l1 < 1.001f);
                     CHECK(row[i0] * l0 + row[i1] * l1 > 0.999f);
