@@ -1,7 +1,7 @@
 // dcl_bilinear.h -- the index arithmetic of bilinear resizing, the only place it is written.  dcl_resize.hip, dcl_upce.hip,
-// dcl_tta.hip, dcl_pred.hip, the plan exports of libdcl_tta / libdcl_pred and the host tests all call these functions, so that
-// training logits, merged test-time-augmentation views and saved predictions agree bit for bit with each other and with
-// F.interpolate.  Host-compilable: plain functions and <math.h>, no HIP header and no library's public header (DCL_BILINEAR_HD is
+// dcl_tta.hip, dcl_pred.hip, dcl_eval.hip, the plan exports of libdcl_tta / libdcl_pred / libdcl_eval and the host tests all call
+// these functions, so that training logits, merged test-time-augmentation views, saved predictions and the evaluation at the
+// original label size agree bit for bit with each other and with F.interpolate.  Host-compilable: plain functions and <math.h>, no HIP header and no library's public header (DCL_BILINEAR_HD is
 // empty unless a HIP compiler reads this, where it lets the kernels call the same code, inlined).
 //
 // The arithmetic restates ATen's (UpSample.h: area_pixel_compute_scale / _source_index, f32):

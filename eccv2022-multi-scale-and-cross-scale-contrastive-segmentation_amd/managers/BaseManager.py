@@ -44,6 +44,10 @@ def set_seeds(seed):
 
 
 class BaseManager:
+    # the datasets whose validation images are resized (resize_val) and scored at their original size: the reference's
+    # post_process_output names PASCALC and ADE20K; PASCAL-Context has no reader here
+    ORIGINAL_SIZE_DATASETS = ('ADE20K',)
+
     def __init__(self, configuration, autostart=True):
         self.config = parse_config(configuration)
         cfg = self.config
@@ -226,9 +230,9 @@ class BaseManager:
                                 self.experiment, seed)
         plan_v = AugmentPlanner(dcfg.get('transforms_val', ['torchvision_normalise']), dcfg.get('transform_values_val', tv),
                                 self.dataset, self.experiment, seed + 1)
-        if plan_v.resize_val:
+        if plan_v.resize_val and self.dataset not in self.ORIGINAL_SIZE_DATASETS:
             printlog("[mscs_amd] transforms_val holds resize_val: validate() will raise (the reference's original-label "
-                     "evaluation is not ported)")
+                     f"evaluation applies to {' and '.join(self.ORIGINAL_SIZE_DATASETS)} only)")
         if dcfg.get('synthetic_raw', False):
             size = dcfg.get('synthetic_raw_size', [1024, 2048])
             train = SyntheticRaw(dcfg.get('synthetic_length', 64), size, self.dataset, self.experiment, plan_t, seed=seed)
@@ -455,14 +459,54 @@ class BaseManager:
             printlog(f'ep {self.epoch} it {batch_num} t:{ms:.0f}ms {terms}')
 
     def _valid_batch(self, batch):
-        """(img, lbl) of a validation batch on the device; on the raw path through the validation plan's geometry."""
+        """(img, lbl, original) of a validation batch on the device; on the raw path through the validation plan's geometry.
+        ``original`` is None, or -- a raw batch whose plan resized (resize_val), on a dataset the reference scores at the original
+        size -- per sample what utils.evaluate.evaluate_at_original needs: the raw label as decoded, (rh, rw), (H, W) and the
+        device copy of the raw id -> network id table."""
         if not isinstance(batch[0], (list, tuple)):
-            return batch[0].to(self.device), batch[1].to(self.device)
-        if any((m['plan'].rh, m['plan'].rw) != (m['plan'].H, m['plan'].W) for m in batch[2]):
+            return batch[0].to(self.device), batch[1].to(self.device), None
+        plans = [m['plan'] for m in batch[2]]
+        resized = any((p.rh, p.rw) != (p.H, p.W) for p in plans)
+        if resized and self.dataset not in self.ORIGINAL_SIZE_DATASETS:
             raise NotImplementedError("validation on resize_val needs the reference's original-label evaluation "
                                       "(Resize(return_original_labels=True)), which is not ported")
         img, lbl, _ = self._upload(*batch[:3])
-        return img, lbl
+        if not resized:
+            return img, lbl, None
+        lut = self._augment._lut_on(self.device)
+        original = [{'label': raw.to(self.device, non_blocking=True), 'crop': (p.rh, p.rw), 'size': (p.H, p.W), 'lut': lut}
+                    for raw, p in zip(batch[1], plans)]
+        return img, lbl, original
+
+    @staticmethod
+    def _main_logits(out):
+        """The main logits of a model's eval-mode return value (a tensor, an UpsampledLogits, or a tuple that holds them)."""
+        logits = out[0] if isinstance(out, (tuple, list)) and len(getattr(out[0], 'shape', ())) == 4 and len(out) == 2 else out
+        if isinstance(logits, (tuple, list)):
+            logits = logits[1]
+        return logits
+
+    def _evaluate_original(self, output, original, cm, want_ids=False):
+        """The reference's post_process_output and the confusion matrix after it, per sample (utils/evaluate.py): crop the
+        fit_stride padding, resize to the original size with the bare model's align_corners, score against lut[raw label].
+        Returns (cm + this batch's counts, [ids uint8 [H, W] per sample] when asked)."""
+        from ..utils.evaluate import evaluate_at_original
+        align = bool(self._bare_model().align_corners)
+        lazy = hasattr(output, 'materialize')
+        ids = []
+        for n, o in enumerate(original):
+            if lazy:
+                one = output if output.lowres.shape[0] == 1 else type(output)(output.lowres[n:n + 1], output.size, output.align_corners)
+            else:
+                one = output[n:n + 1]
+            ret = evaluate_at_original(one, o['label'], o['crop'], o['size'], align, self.dataset, label_lut=o['lut'],
+                                       existing_matrix=cm if torch.is_tensor(cm) else None, return_ids=want_ids)
+            if want_ids:
+                cm, i = ret
+                ids.append(i[0])
+            else:
+                cm = ret
+        return cm, ids
 
     @torch.no_grad()
     def validate(self):
@@ -473,14 +517,23 @@ class BaseManager:
         panels = self._panel_writer() if self.config.get('save_valid_images', False) else None
         try:
             for i, batch in enumerate(self.data_loaders['valid_loader']):
-                img, lbl = self._valid_batch(batch)
-                out = self._bare_model()(img.float())
-                logits = out[0] if isinstance(out, (tuple, list)) and out[0].dim() == 4 and len(out) == 2 else out
-                if isinstance(logits, (tuple, list)):
-                    logits = logits[1]
-                cm = cm + t_get_confusion_matrix(logits, lbl, self.dataset)
-                if panels is not None:
-                    self._save_panel(panels, i, img, lbl, logits)
+                img, lbl, original = self._valid_batch(batch)
+                if original is not None:
+                    # scored at the original size; with graph.lazy_logits the model hands out its 1/4 map for it
+                    bare = self._bare_model()
+                    lazy = self.config['graph'].get('lazy_logits', False)
+                    logits = self._main_logits(self._call_lazy(bare, img.float()) if lazy else bare(img.float()))
+                    cm, ids = self._evaluate_original(logits, original, cm, want_ids=panels is not None)
+                    if panels is not None:
+                        self._save_panel_original(panels, i, img, original[0], ids[0])
+                else:
+                    out = self._bare_model()(img.float())
+                    logits = out[0] if isinstance(out, (tuple, list)) and out[0].dim() == 4 and len(out) == 2 else out
+                    if isinstance(logits, (tuple, list)):
+                        logits = logits[1]
+                    cm = cm + t_get_confusion_matrix(logits, lbl, self.dataset)
+                    if panels is not None:
+                        self._save_panel(panels, i, img, lbl, logits)
                 if i + 1 >= self.config.get('max_valid_imgs', 10):
                     break
         finally:
@@ -525,6 +578,21 @@ class BaseManager:
         ids = predict_maps(first)[0]
         ignore = ignore_class(self.dataset, self.experiment)
         panel = panel_image(img[0].float(), lbl[0], ids[0], palette, label_ignore=ignore, ids_ignore=ignore)
+        writer.write('record_{:02d}_step{}.png'.format(rec, self.global_step), panel)
+
+    def _save_panel_original(self, panels, rec, img, original, ids):
+        """The panel of a record that was scored at its original size: the image is the network input without its padding, resized
+        like the logits (three channels; the reference's post_process_output does the same), the label is lut[raw label]."""
+        import torch.nn.functional as F
+        from ..utils import ignore_class
+        from ..utils.predict import panel_image
+        writer, palette = panels
+        (rh, rw), size = original['crop'], original['size']
+        image = F.interpolate(img[:1, :, :rh, :rw].float(), size=size, mode='bilinear',
+                              align_corners=bool(self._bare_model().align_corners))[0]
+        label = original['lut'][original['label'].to(torch.int64)]
+        ignore = ignore_class(self.dataset, self.experiment)
+        panel = panel_image(image, label, ids, palette, label_ignore=ignore, ids_ignore=ignore)
         writer.write('record_{:02d}_step{}.png'.format(rec, self.global_step), panel)
 
     @staticmethod
@@ -581,8 +649,10 @@ class BaseManager:
         """Run the model over ``valid_loader`` the way the reference's ``infer()`` does (BaseManager.py:585-675): the checkpoint
         named by ``load_checkpoint`` (``load_last``: the last instead of the best one), with ``tta`` the model inside a test-time
         augmentation wrapper (``tta_scales``, ``strides``, ``flip``, ``data.transform_values.crop_shape``), the confusion matrix
-        summed over the images.  Returns the metrics dict of ``t_get_mean_iou`` and logs the mIoU on rank 0.  No
-        ``post_process_output`` step.  ``save_outputs: true`` (rank 0) writes, per image, the reference's two files
+        summed over the images.  Returns the metrics dict of ``t_get_mean_iou`` and logs the mIoU on rank 0.  The reference's
+        ``post_process_output`` step (ADE20K on ``resize_val``: padding cut off, logits resized to the image's original size, scored
+        against the label that was never resized) is one kernel per image after the model or the wrapper (utils/evaluate.py), and
+        the saved files are then at the original size.  ``save_outputs: true`` (rank 0) writes, per image, the reference's two files
         (BaseManager.py:677-699): <log_dir>/outputs/<split>/debug/<stem>.png (colours) and .../submit/<stem>.png (dataset class
         ids), through utils/predict.py: without tta the model is then called with ``lazy_eval_logits`` and prediction and
         confusion matrix both come from its 1/4-resolution map."""
@@ -610,18 +680,30 @@ class BaseManager:
             saved = 0
         try:
             for rec_num, batch in enumerate(self.data_loaders['valid_loader']):
-                img, lbl = self._valid_batch(batch)
-                if writer is None:
-                    output = tta_model(img.float()) if tta_model is not None else bare(img.float())
-                else:
+                img, lbl, original = self._valid_batch(batch)
+                if original is not None:
+                    # the reference's post_process_output: files and matrix at the image's original size, from one kernel per
+                    # image that reads the model's 1/4 map (or a wrapper's dense output)
                     output = tta_model(img.float()) if tta_model is not None else self._call_lazy(bare, img.float())
-                    _, mapped, rgb = predict_maps(output, lut, palette)     # (leaves output.pred for the confusion matrix)
-                    for n in range(mapped.shape[0]):
+                    confusion_matrix, ids = self._evaluate_original(self._main_logits(output), original, confusion_matrix,
+                                                                    want_ids=writer is not None)
+                    for n, one in enumerate(ids):
                         stem = self._record_stem(batch, n, saved)
-                        writer.write(os.path.join('debug', stem + '.png'), rgb[n])
-                        writer.write(os.path.join('submit', stem + '.png'), mapped[n])
+                        writer.write(os.path.join('debug', stem + '.png'), palette[one.to(torch.int64)])
+                        writer.write(os.path.join('submit', stem + '.png'), lut[one.to(torch.int64)])
                         saved += 1
-                confusion_matrix = t_get_confusion_matrix(output, lbl, self.dataset, confusion_matrix)
+                else:
+                    if writer is None:
+                        output = tta_model(img.float()) if tta_model is not None else bare(img.float())
+                    else:
+                        output = tta_model(img.float()) if tta_model is not None else self._call_lazy(bare, img.float())
+                        _, mapped, rgb = predict_maps(output, lut, palette)     # (leaves output.pred for the confusion matrix)
+                        for n in range(mapped.shape[0]):
+                            stem = self._record_stem(batch, n, saved)
+                            writer.write(os.path.join('debug', stem + '.png'), rgb[n])
+                            writer.write(os.path.join('submit', stem + '.png'), mapped[n])
+                            saved += 1
+                    confusion_matrix = t_get_confusion_matrix(output, lbl, self.dataset, confusion_matrix)
                 if rec_num == 10 and self.debugging:
                     break
         finally:
