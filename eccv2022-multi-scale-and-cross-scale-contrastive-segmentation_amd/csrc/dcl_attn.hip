@@ -41,38 +41,9 @@ struct AttnArgs {
 
 #define AMFMA(A, B, C) __builtin_amdgcn_mfma_f32_32x32x16_f16(as_half8(A), as_half8(B), (C), 0, 0, 0)
 
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 __device__ __forceinline__ float uniform(float v)
 {
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-
-// 8 floats -> MFMA operand fragments (hi, lo)
-__device__ __forceinline__ void split8(const float (&v)[8], float s, u32x4 &hi, u32x4 &lo)
-{
-    unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-    split2(v[0], v[1], s, h0, l0);
-    split2(v[2], v[3], s, h1, l1);
-    split2(v[4], v[5], s, h2, l2);
-    split2(v[6], v[7], s, h3, l3);
-    hi = u32x4{h0, h1, h2, h3};
-    lo = u32x4{l0, l1, l2, l3};
-}
-
-// The splits are inline asm: the compiler's hazard recognizer does not see a VALU write behind them (dcl_winattn_mfma.hip);
-// a fenced s_nop between the splits and the MFMAs that consume them.
-__device__ __forceinline__ void split_to_mfma_fence()
-{
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 4");
-    __builtin_amdgcn_sched_barrier(0);
 }
 
 // e^x for x <= 0 to about one ulp: the rounding error of x log2(e) is carried into the result (v_exp_f32 alone would leave

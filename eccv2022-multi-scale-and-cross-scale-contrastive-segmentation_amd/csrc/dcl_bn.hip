@@ -234,9 +234,7 @@ __global__ void k_bn_finalize(const float *__restrict__ sums, int C, double coun
 __device__ __forceinline__ void block_amax(float m, float *dst)
 {
     __shared__ float wmax[BN_THREADS / 64];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        m = fmaxf(m, __shfl_xor(m, o, 64));
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0)
         wmax[threadIdx.x >> 6] = m;
     // raw barrier behind an LDS-only wait: __syncthreads() also waits for the wave's outstanding STORES (they count in

@@ -39,6 +39,13 @@ __device__ inline float wave_sum(float v)
         v += __shfl_xor(v, o, 64);
     return v;
 }
+__device__ __forceinline__ float wave_max(float v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1)
+        v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
 __device__ inline int wave_min_i(int v)
 {
 #pragma unroll

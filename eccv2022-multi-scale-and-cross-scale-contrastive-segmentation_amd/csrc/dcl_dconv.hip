@@ -39,17 +39,6 @@ __global__ __launch_bounds__(NTHR) void k_absmax(const float *__restrict__ x, in
         atomicMax(slot, m);
 }
 
-__device__ __forceinline__ void split8(const float (&v)[8], float s, u32x4 &hi, u32x4 &lo)
-{
-    unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-    split2(v[0], v[1], s, h0, l0);
-    split2(v[2], v[3], s, h1, l1);
-    split2(v[4], v[5], s, h2, l2);
-    split2(v[6], v[7], s, h3, l3);
-    hi = u32x4{h0, h1, h2, h3};
-    lo = u32x4{l0, l1, l2, l3};
-}
-
 // one thread per lane of one fragment: [tap][row tile][chunk][hi, lo][lane] x 16 bytes
 __global__ __launch_bounds__(NTHR) void k_pack(const float *__restrict__ w, int Co, int Ci, const float *__restrict__ wamax,
                                                 u32x4 *__restrict__ wp, int transposed)
@@ -127,6 +116,7 @@ __global__ __launch_bounds__(NTHR) void k_dconv(ConvArgs a)
                 v[j] = valid ? xc[(size_t)j * HW] : 0.f;
             u32x4 bhi, blo;
             split8(v, sx, bhi, blo);
+            split_to_mfma_pad(bhi, blo);
             const u32x4 ahi = wt[(size_t)ch * 128], alo = wt[(size_t)ch * 128 + 64];
             acc0 = DMFMA(ahi, bhi, acc0);
             acc0 = DMFMA(ahi, blo, acc0);

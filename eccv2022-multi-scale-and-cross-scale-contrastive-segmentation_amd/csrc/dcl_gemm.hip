@@ -656,9 +656,7 @@ __global__ __launch_bounds__(256) void k_gemm_slab_sum(const float *__restrict__
         mx = fmaxf(mx, fmaxf(fmaxf(fabsf(s.x), fabsf(s.y)), fmaxf(fabsf(s.z), fabsf(s.w))));
     }
     if (c_amax) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1)
-            mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+        mx = wave_max(mx);
         // one atomic per wave at most, and only while it would still raise the maximum (a plain read first: tens of
         // thousands of same-address atomics serialise in L2 -- 0.4 ms on a 6400 x 1536 result)
         if ((threadIdx.x & 63) == 0 && mx > __builtin_nontemporal_load(c_amax))

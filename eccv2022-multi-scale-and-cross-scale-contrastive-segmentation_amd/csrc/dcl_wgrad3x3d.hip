@@ -492,6 +492,7 @@ __global__ __launch_bounds__(256, 1) void k_wgrad1x1d(Wgrad1Args a)
             split2(src[1].z, src[1].w, scale, h[3], l[3]);
             dst[0] = as_half8(u32x4{h[0], h[1], h[2], h[3]});
             dst[1] = as_half8(u32x4{l[0], l[1], l[2], l[3]});
+            split_to_mfma_pad(dst[0], dst[1]);      // the next step's MFMAs can follow at once
         };
 
         half8 FA[2][NCO][2], FB[2][NCI][2];

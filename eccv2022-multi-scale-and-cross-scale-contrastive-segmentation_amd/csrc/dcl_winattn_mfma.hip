@@ -15,15 +15,12 @@
 //                   kappa(s, half, t) = 16 s + 8 (t / 4) + 4 half + t % 4; the A fragment (V^T) is gathered in the same
 //                   order, 8 dword loads per k-step with the lanes along the 32 channels of a v row (128-byte segments).
 // The zero-padded border tokens carry qkv = the projection's bias, shifted windows mask by region id, as in dcl_winattn.hip.
-#include "dcl_common.h"
+#include "dcl_f16x3.h"
 
 namespace {
 
 constexpr int WS = 7, NT = 49, HD = 32;
 constexpr int BST = 52;                 // row stride of the bias table in LDS (16-byte groups, conflict-free b128 reads)
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
 struct WmArgs {
     const float *qkv;       // [B, H*W, 3*C]
@@ -51,56 +48,13 @@ __device__ __forceinline__ void token_of_m(const WmArgs &a, int wy, int wx, int 
     rid = ry * 3 + rx;
 }
 
-__device__ __forceinline__ float pow2_scale_w(float amax)
-{
-    return amax == 0.f ? 1.f : exp2f(fminf(fmaxf(floorf(log2f(16384.0f / amax)), -100.f), 100.f));
-}
-
-__device__ __forceinline__ void split2w(float v0, float v1, float s, unsigned &hi, unsigned &lo)
-{
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(hi) : "v"(v0), "v"(s));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(hi) : "v"(v1), "v"(s));
-    asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=&v"(lo) : "v"(v0), "v"(s), "v"(hi));
-    asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(v1), "v"(s), "v"(hi));
-}
-
-// 8 floats -> MFMA operand fragments (hi, lo)
-__device__ __forceinline__ void split8(const float (&v)[8], float s, h8 &hi, h8 &lo)
-{
-    unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-    split2w(v[0], v[1], s, h0, l0);
-    split2w(v[2], v[3], s, h1, l1);
-    split2w(v[4], v[5], s, h2, l2);
-    split2w(v[6], v[7], s, h3, l3);
-    hi = __builtin_bit_cast(h8, u32x4v{h0, h1, h2, h3});
-    lo = __builtin_bit_cast(h8, u32x4v{l0, l1, l2, l3});
-}
-
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 __device__ __forceinline__ void wave_lds_sync()
 {
     __builtin_amdgcn_s_waitcnt(0xc07f);                   // lgkmcnt(0)
     __builtin_amdgcn_wave_barrier();
 }
 
-#define WMFMA(A, B, C) __builtin_amdgcn_mfma_f32_32x32x16_f16((A), (B), (C), 0, 0, 0)
-
-// The splits are inline asm: the compiler's hazard recognizer does not see a VALU write behind them, so an MFMA that reads
-// a fragment right after its last v_fma_mixhi gets no wait states and can read the register before the high half has
-// landed (observed: 1e-4 errors in one of ~10^5 scores).  A fenced s_nop between the splits and the MFMAs that consume them.
-__device__ __forceinline__ void split_to_mfma_fence()
-{
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 4");
-    __builtin_amdgcn_sched_barrier(0);
-}
+#define WMFMA(A, B, C) __builtin_amdgcn_mfma_f32_32x32x16_f16(as_half8(A), as_half8(B), (C), 0, 0, 0)
 
 __global__ __launch_bounds__(64) void k_winattn_fwd_mfma(WmArgs a)
 {
@@ -176,8 +130,8 @@ __global__ __launch_bounds__(64) void k_winattn_fwd_mfma(WmArgs a)
                     mv = fmaxf(mv, fabsf(x));
                 }
             }
-        const float sq = pow2_scale_w(wave_max(mq)), sk = pow2_scale_w(wave_max(mk));
-        h8 qh[2][2], ql[2][2], kh[2][2], kl[2][2];
+        const float sq = pow2_scale(wave_max(mq)), sk = pow2_scale(wave_max(mk));
+        u32x4 qh[2][2], ql[2][2], kh[2][2], kl[2][2];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -268,12 +222,12 @@ __global__ __launch_bounds__(64) void k_winattn_fwd_mfma(WmArgs a)
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 ot[j][r] = 0.f;
-        const float sv = pow2_scale_w(wave_max(mv));
+        const float sv = pow2_scale(wave_max(mv));
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                h8 vh, vl;
+                u32x4 vh, vl;
                 split8(vv[2 * i + s], sv, vh, vl);
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
@@ -281,7 +235,7 @@ __global__ __launch_bounds__(64) void k_winattn_fwd_mfma(WmArgs a)
 #pragma unroll
                     for (int t = 0; t < 8; ++t)
                         pp[t] = st[i][j][8 * s + t];
-                    h8 ph, pl;
+                    u32x4 ph, pl;
                     split8(pp, 1.0f, ph, pl);
                     split_to_mfma_fence();
                     ot[j] = WMFMA(vh, pl, ot[j]);
@@ -386,7 +340,7 @@ __global__ __launch_bounds__(64) void k_winattn_bwd_mfma(WbArgs a)
         wave_lds_sync();
         const int tok[2] = {Ts[l32], Ts[32 + l32]};
         // ---- fragments of Q, K, V (qkv rows, or the projection's bias for padded tokens) and dO (zero unless real)
-        h8 fh[4][2][2], fl[4][2][2];            // [q k v do][tile][k-step]
+        u32x4 fh[4][2][2], fl[4][2][2];            // [q k v do][tile][k-step]
         float fs[4];
         {
             float raw[4][2][2][8];
@@ -415,7 +369,7 @@ __global__ __launch_bounds__(64) void k_winattn_bwd_mfma(WbArgs a)
             }
 #pragma unroll
             for (int X = 0; X < 4; ++X) {
-                fs[X] = pow2_scale_w(wave_max(mxv[X]));
+                fs[X] = pow2_scale(wave_max(mxv[X]));
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -481,12 +435,12 @@ __global__ __launch_bounds__(64) void k_winattn_bwd_mfma(WbArgs a)
                         xv[2 * i + s][t] = v;
                         mx = fmaxf(mx, fabsf(v));
                     }
-            const float xs = pow2_scale_w(wave_max(mx));
+            const float xs = pow2_scale(wave_max(mx));
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
-                    h8 xh, xl;
+                    u32x4 xh, xl;
                     split8(xv[2 * i + s], xs, xh, xl);
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
@@ -494,7 +448,7 @@ __global__ __launch_bounds__(64) void k_winattn_bwd_mfma(WbArgs a)
 #pragma unroll
                         for (int t = 0; t < 8; ++t)
                             pp[t] = m[i][j][8 * s + t];
-                        h8 ph, pl;
+                        u32x4 ph, pl;
                         split8(pp, ms, ph, pl);
                         split_to_mfma_fence();
                         o[j] = WMFMA(xh, pl, o[j]);
@@ -599,7 +553,7 @@ __global__ __launch_bounds__(64) void k_winattn_bwd_mfma(WbArgs a)
                     }
                 }
         }
-        const float sds = pow2_scale_w(wave_max(dsmax));
+        const float sds = pow2_scale(wave_max(dsmax));
         wave_lds_sync();                                  // K rows are in the tile, delta table written
         {
             f32x16 o[2];
@@ -638,7 +592,7 @@ __global__ __launch_bounds__(64) void k_winattn_bwd_mfma(WbArgs a)
                     }
                 }
         }
-        const float sds2 = pow2_scale_w(wave_max(dsmax));
+        const float sds2 = pow2_scale(wave_max(dsmax));
         {
             f32x16 o[2];
             to_tile(3);                                   // dO rows
