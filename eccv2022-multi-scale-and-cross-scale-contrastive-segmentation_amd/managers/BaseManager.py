@@ -717,6 +717,67 @@ class BaseManager:
             printlog(msg_str)
         return mious
 
+    # ------------------------------------------------------------------ demo_tsne (utils/tsne.py)
+    TSNE_SCALES = {4: 0, 8: 1, 16: 2, 32: 3}
+
+    def _tsne_feature_map(self, bare, backbone_out, s):
+        """The feature map at pyramid level ``s`` out of what the bare model's ``backbone`` returned."""
+        name = self.config['graph']['model']
+        if name == 'HRNet':
+            if bare.backbone.return_all_scales:
+                return backbone_out[1][s]
+            if s != 0:
+                raise ValueError("demo_tsne: an HRNet without ms_projector / return_all_scales hands out its concatenated map "
+                                 "only: tsne_scale must be 4")
+            return backbone_out.materialize() if hasattr(backbone_out, 'materialize') else backbone_out
+        from ..models.Swin import as_nchw
+        return as_nchw(backbone_out[s])
+
+    @torch.no_grad()
+    def demo_tsne(self):
+        """The reference's ``demo_tsne`` mode (BaseManager.py:701-783): the checkpoint named by ``load_checkpoint`` (``load_last``:
+        the last instead of the best one), the model in eval mode over ``valid_loader``, per image up to a few pixels of every
+        class out of the backbone's feature map at stride ``tsne_scale`` (4, 8, 16 or 32; caught by a forward hook on the bare
+        model's ``backbone``), then the exact t-SNE of what was gathered (utils/tsne.py) and the scatter plot
+        ``<run_id>_perp-<p>_its-<n>_feats-per-class-<f>_scale<s>.png`` under the log directory, an ``.npz`` beside it.  Optional
+        keys ``tsne_iters``, ``tsne_perplexity``, ``tsne_feats_per_class`` default to the reference's 2000, 30 and 1000.  Any
+        batch size (the reference asserts 1): one sample at a time.  Returns the embedding [N, 2] (numpy)."""
+        cfg = self.config
+        assert 'load_checkpoint' in cfg, 'load_checkpoint: "run_id" must be in config for demo_tsne mode!'
+        from ..utils.tsne import TsneManager
+        name = cfg['graph']['model']
+        if name not in ('HRNet', 'UPerNet'):
+            raise NotImplementedError(f"demo_tsne: no feature pyramid is defined for model {name} (HRNet and UPerNet, as in the reference)")
+        scale = int(cfg.get('tsne_scale', 4))
+        if scale not in self.TSNE_SCALES:
+            raise ValueError(f"tsne_scale must be one of {sorted(self.TSNE_SCALES)}, got {scale}")
+        self.model.eval()
+        bare = self._bare_model()
+        self.load_checkpoint(cfg['load_checkpoint'], 'last' if cfg.get('load_last', False) else 'best')
+        run_id = cfg.get('run_id') or os.path.basename(self._log_dir())
+        self.TsneManager = TsneManager(self.dataset, bare.num_classes, scale=scale, run_id=run_id,
+                                       perplexity=cfg.get('tsne_perplexity', 30), iters=cfg.get('tsne_iters', 2000),
+                                       feats_per_class=cfg.get('tsne_feats_per_class', 1000), seed=cfg['seed'],
+                                       experiment=self.experiment, palette=cfg['data'].get('palette'))
+        caught = {}
+        hook = bare.backbone.register_forward_hook(lambda _m, _i, out: caught.__setitem__('out', out))
+        try:
+            for rec_num, batch in enumerate(self.data_loaders['valid_loader']):
+                img, lbl, _ = self._valid_batch(batch)
+                for n in range(img.shape[0]):
+                    self.model(img[n:n + 1].float())
+                    if img.is_cuda:
+                        torch.cuda.synchronize(self.device)        # the pyramid levels come from the branches' own streams
+                    f = self._tsne_feature_map(bare, caught.pop('out'), self.TSNE_SCALES[scale])
+                    self.TsneManager.accumulate(f, lbl[n:n + 1])
+                if rec_num == 100 and self.debugging:
+                    break
+        finally:
+            hook.remove()
+        printlog(f'computing tsne for feats of scale : {scale} dim : {self.TsneManager.feat_dim} '
+                 f'counts : {list(enumerate(self.TsneManager.counts))}')
+        return self.TsneManager.compute(self._log_dir())
+
     # ------------------------------------------------------------------ checkpoints
     def _log_dir(self):
         """``<log_path>/<run_id>`` like the reference (LoggingManager.py:81-91); created on first use so that runs
