@@ -92,6 +92,30 @@ class ADE20K(_Raw):
             self.targets.append(target)
 
 
+class PascalC(_Raw):
+    """``<root>/<split>/image/*.jpg`` paired by stem with ``<root>/<split>/label/*.png`` (the reference's datasets/PascalC.py);
+    ``split`` is 'train' or 'val'.  Raw ids: in experiment 1 raw 0 is the ignore class and raw k is class k - 1 of 59."""
+    dataset, experiment = 'PASCALC', 1
+
+    def __init__(self, root, split='train', planner=None):
+        super().__init__(planner)
+        assert split in ('train', 'val'), f'split {split} is not valid'
+        self.root, self.split = root, split
+        images_dir, targets_dir = os.path.join(root, split, 'image'), os.path.join(root, split, 'label')
+        self.images, self.targets = [], []
+        for name in sorted(os.listdir(images_dir)):
+            stem, ext = os.path.splitext(name)
+            if ext.lower() not in ('.jpg', '.jpeg'):
+                continue
+            target = os.path.join(targets_dir, stem + '.png')
+            if not os.path.exists(target):
+                raise FileNotFoundError(f'{target} (the label of {name}) not found')
+            self.images.append(os.path.join(images_dir, name))
+            self.targets.append(target)
+        labels = sorted(n for n in os.listdir(targets_dir) if n.lower().endswith('.png'))
+        assert len(labels) == len(self.targets), f'{targets_dir}: {len(labels)} labels for {len(self.images)} images'
+
+
 class SyntheticRaw(_Raw):
     """uint8 images and blocky uint8 labels in the RAW ids of ``dataset`` (the ids its lookup table maps to a class, and the first
     unmapped one for the ignore class), without touching disk."""

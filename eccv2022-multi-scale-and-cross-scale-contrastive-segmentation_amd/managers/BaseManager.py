@@ -45,8 +45,8 @@ def set_seeds(seed):
 
 class BaseManager:
     # the datasets whose validation images are resized (resize_val) and scored at their original size: the reference's
-    # post_process_output names PASCALC and ADE20K; PASCAL-Context has no reader here
-    ORIGINAL_SIZE_DATASETS = ('ADE20K',)
+    # post_process_output names PASCALC and ADE20K
+    ORIGINAL_SIZE_DATASETS = ('ADE20K', 'PASCALC')
 
     def __init__(self, configuration, autostart=True):
         self.config = parse_config(configuration)
@@ -223,7 +223,7 @@ class BaseManager:
     def _load_raw_data(self):
         """The raw input path (datasets/raw.py, datasets/augment.py): the loaders only decode files (or draw ``synthetic_raw``
         pixels) and attach each sample's augmentation plan; ``_upload`` runs the augmentation on the device."""
-        from ..datasets import ADE20K, AugmentPlanner, Cityscapes, DeviceAugment, SyntheticRaw, list_collate, network_lut
+        from ..datasets import ADE20K, AugmentPlanner, Cityscapes, DeviceAugment, PascalC, SyntheticRaw, list_collate, network_lut
         dcfg, seed = self.config['data'], self.config['seed']
         tv = dcfg.get('transform_values', {})
         plan_t = AugmentPlanner(dcfg.get('transforms', ['RandomCropImgLbl', 'torchvision_normalise']), tv, self.dataset,
@@ -249,8 +249,12 @@ class BaseManager:
             elif self.dataset == 'ADE20K':
                 split = dcfg.get('split', ['train', 'val'])
                 train, valid = ADE20K(root, split[0], plan_t), ADE20K(root, split[1], plan_v)
+            elif self.dataset == 'PASCALC':
+                split = dcfg.get('split', ['train', 'val'])
+                train, valid = PascalC(root, split[0], plan_t), PascalC(root, split[1], plan_v)
             else:
-                raise NotImplementedError(f"no reader for dataset {self.dataset}: CITYSCAPES and ADE20K are ported (SURVEY.md row 15)")
+                raise NotImplementedError(f"no reader for dataset {self.dataset}: CITYSCAPES, ADE20K and PASCALC are ported "
+                                          "(SURVEY.md row 15)")
         self._augment = DeviceAugment(network_lut(self.dataset, self.experiment))
         sampler = DistributedSampler(train, num_replicas=self.world_size, rank=self.rank) if self.parallel else None
         self.samplers['train_loader'] = sampler
@@ -644,13 +648,33 @@ class BaseManager:
                                       "hard-coded (2048 s, 512 s)) is not ported; drop `strides` from the config for TTAWrapper")
         return _models.TTAWrapper(self.model, scales_list)
 
+    def _tta_wrapper(self):
+        """What ``infer()`` wraps the model in: the two sliding-window protocols with equal-size windows (models/TTA.py, fused on
+        libdcl_slide.so) -- PASCALC -> TTAWrapperPC, ADE20K with ``strides`` -> TTAWrapperSlide -- and ``_tta_model()`` for the
+        rest.  ``tta_window_batch`` (default 8): windows per model call on their fused path."""
+        cfg = self.config
+        sliding = self.dataset == 'PASCALC' or (self.dataset == 'ADE20K' and 'strides' in cfg)
+        if not sliding:
+            return self._tta_model()
+        scales_list = [0.75, 1.25, 1.5, 1.75, 2] if not self.debugging else [1.0]
+        if 'tta_scales' in cfg and not self.debugging:
+            scales_list = cfg['tta_scales']
+        if self.dataset == 'PASCALC':
+            wrapper = _models.TTAWrapperPC(self.model, scales_list, num_classes=self._bare_model().num_classes)
+        else:
+            crop_size = cfg['data']['transform_values']['crop_shape']
+            flip = cfg['flip'] if 'flip' in cfg else True
+            wrapper = _models.TTAWrapperSlide(self.model, scales_list, flip, cfg['strides'], crop_size)
+        wrapper.tta_window_batch = int(cfg.get('tta_window_batch', 8))
+        return wrapper
+
     @torch.no_grad()
     def infer(self):
         """Run the model over ``valid_loader`` the way the reference's ``infer()`` does (BaseManager.py:585-675): the checkpoint
         named by ``load_checkpoint`` (``load_last``: the last instead of the best one), with ``tta`` the model inside a test-time
         augmentation wrapper (``tta_scales``, ``strides``, ``flip``, ``data.transform_values.crop_shape``), the confusion matrix
         summed over the images.  Returns the metrics dict of ``t_get_mean_iou`` and logs the mIoU on rank 0.  The reference's
-        ``post_process_output`` step (ADE20K on ``resize_val``: padding cut off, logits resized to the image's original size, scored
+        ``post_process_output`` step (ADE20K and PASCALC on ``resize_val``: padding cut off, logits resized to the image's original size, scored
         against the label that was never resized) is one kernel per image after the model or the wrapper (utils/evaluate.py), and
         the saved files are then at the original size.  ``save_outputs: true`` (rank 0) writes, per image, the reference's two files
         (BaseManager.py:677-699): <log_dir>/outputs/<split>/debug/<stem>.png (colours) and .../submit/<stem>.png (dataset class
@@ -666,7 +690,7 @@ class BaseManager:
         self.load_checkpoint(cfg['load_checkpoint'], 'last' if cfg.get('load_last', False) else 'best')
         tta_model = None
         if cfg['tta']:
-            tta_model = self._tta_model()
+            tta_model = self._tta_wrapper()
             printlog(f'** {tta_model.__class__.__name__} using tta with transforms \n ** flip and scales: {tta_model.scales}')
         confusion_matrix = None
         writer = None

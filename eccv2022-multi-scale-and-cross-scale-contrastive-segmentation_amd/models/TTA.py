@@ -13,14 +13,27 @@ Kept quirks of the reference: 1.0 is appended to the caller's ``scale_list`` in 
 but always runs both orientations (``f == 0`` is the mirrored one) and resizes every view to the image size even at equal size;
 ``TTAWrapperCTS`` takes exp of the averaged logits, not a softmax, and does not divide the sum over the scales.  Not kept: a
 DDP-wrapped model is unwrapped with ``model.module`` (the reference writes ``ddp.module``), the cv2 image dumps of ``debug`` are
-gone, and a window grid with no rows or columns raises instead of dividing by a zero count."""
+gone, and a window grid with no rows or columns raises instead of dividing by a zero count.
+
+``TTAWrapperPC`` (models/TTA_wrapper_PC.py: PASCAL-Context) and ``TTAWrapperSlide`` (models/TTAWrapperSlide.py: ADE20K with
+``strides``) are sliding-window protocols whose windows all have one size per scale: PASCAL-Context pads the image and its partial
+windows to the crop with ``-mean / std`` and does not shift the last window back, the ADE20K protocol shifts it back.  Their fused
+path (``debug.cfg.slide_hip``, models/ops_slide.py on libdcl_slide.so) is, per view, one launch that writes the crop batch and its
+mirrors from the original image, the model over that batch in chunks of ``tta_window_batch`` windows (a window and its mirror in
+the same call), one launch that writes the averaged canvas, and the ``merge`` above with an identity inner level.  Kept quirks of
+``TTAWrapperSlide``: every image is resized to ``(int(img_scale[0] * s), int(img_scale[1] * s))`` read as (height, width), whatever
+its own size; with ``flip`` every scale is summed twice, once averaged with its mirror and once plain; an axis shorter than the
+crop gives one short window; the sum over the views is not divided.  Kept of ``TTAWrapperPC``: it always flips, and its three
+branches (whole image no larger than the crop, one side shorter, windows) are the reference's.  Not kept: a grid with no window
+raises ``ValueError`` as ``TTAWrapperCTS`` does instead of dividing by zero, and the reference's timing print and image dumps are
+gone."""
 import torch
 import torch.nn.functional as F
 from torch import nn
 from torch.nn.parallel import DistributedDataParallel as ddp
 
 from ..utils import printlog
-from . import ops_tta
+from . import ops_slide, ops_tta
 
 
 class TTAWrapper(nn.Module):
@@ -175,6 +188,165 @@ class TTAWrapperCTS(TTAWrapper):
                         preds[:, :, h0:h1, w0:w1] += pred[:, :, 0:h1 - h0, 0:w1 - w0]
                         count[:, :, h0:h1, w0:w1] += 1
                 preds = preds / count
+            preds = F.interpolate(preds, (ori_height, ori_width), mode='bilinear', align_corners=self.align_corners)
+            final_pred += preds
+        return final_pred
+
+
+class _EqualWindows(TTAWrapper):
+    """What TTAWrapperPC and TTAWrapperSlide share: the per-window ``inference`` of the composition and one fused view."""
+    tta_window_batch = 8                # windows per model call on the fused path (config key of the same name)
+    inference = TTAWrapperCTS.inference
+
+    def _fused_view(self, x, final_pred, size, rows_lo, cols_lo, win, pad, mirror):
+        """One view on the kernels: final_pred [1, C, H, W] += resize(mean over the windows of exp(.)); False, with nothing
+        written, where a kernel refuses the shapes or the model's output is not a window-size map."""
+        C = self.num_classes
+        N = len(rows_lo) * len(cols_lo)
+        out_hw = final_pred.shape[-2:]
+        if not ops_slide.supported(x, C, win, win, rows_lo, cols_lo, size):
+            return False
+        from .. import _lib_tta as lt
+        if not lt.supported(C, int(size[0]), int(size[1]), int(size[0]), int(size[1]), int(out_hw[0]), int(out_hw[1])):
+            return False
+        batch = ops_slide.crops(x[0], size, rows_lo, cols_lo, win, pad, mirror)
+        step = max(int(self.tta_window_batch), 1)
+        z = None
+        for i0 in range(0, N, step):
+            i1 = min(i0 + step, N)
+            inp = torch.cat([batch[i0:i1], batch[N + i0:N + i1]]) if mirror else batch[i0:i1]
+            zc, zsize, align = ops_tta.view_logits(self._call_model(inp, True))
+            if tuple(zsize) != tuple(win) or zc.dim() != 4 or zc.shape[1] != C or zc.dtype != torch.float32:
+                return False
+            if z is None:
+                z = zc.new_empty((2 if mirror else 1, N) + tuple(zc.shape[1:]))
+                z_align = align
+                if not ops_slide.supported(x, C, zc.shape[-2:], win, rows_lo, cols_lo, size):
+                    return False
+            if tuple(zc.shape[1:]) != tuple(z.shape[2:]) or align != z_align:
+                return False
+            z[0, i0:i1] = zc[:i1 - i0]
+            if mirror:
+                z[1, i0:i1] = zc[i1 - i0:]
+        canvas = final_pred.new_empty((C, int(size[0]), int(size[1])))
+        ops_slide.gather(z[0], z[1] if mirror else None, win, z_align, rows_lo, cols_lo, canvas)
+        ops_tta.merge(canvas, size, False, False, final_pred[0], self.align_corners)
+        return True
+
+
+class TTAWrapperPC(_EqualWindows):
+    MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+    def __init__(self, model, scale_list, *, num_classes=59, crop_size=(512, 512), base_size=520):
+        super().__init__(model, scale_list)
+        self.num_classes = num_classes
+        self.crop_size = crop_size
+        self.base_size = base_size
+
+    @property
+    def padvalue(self):
+        return [-1.0 * m / s for m, s in zip(self.MEAN, self.STD)]
+
+    def _plan(self, scale, ori_height, ori_width):
+        """(height, width) of the resized image and the windows [(lo, hi), ...] of its axes padded to the crop"""
+        height, width = ops_tta.cts_size(ori_height, ori_width, self.base_size, scale)
+        crop = (int(self.crop_size[0]), int(self.crop_size[1]))
+        strides = ops_slide.pc_strides(crop)
+        if min(strides) < 1:
+            raise ValueError(f'TTAWrapperPC: crop {list(crop)} gives strides {list(strides)}: the window count would be undefined')
+        rows = ops_slide.pc_windows_1d(max(height, crop[0]), crop[0], strides[0])
+        cols = ops_slide.pc_windows_1d(max(width, crop[1]), crop[1], strides[1])
+        return height, width, rows, cols
+
+    def forward(self, x, ind=0):
+        x = self._input(x)
+        batch, _, ori_height, ori_width = x.size()
+        assert batch == 1, "only supporting batchsize 1."
+        assert x.shape[1] == len(self.MEAN), 'the border value is that of a normalised RGB image'
+        fused = ops_slide.hip_applies(x)
+        crop = (int(self.crop_size[0]), int(self.crop_size[1]))
+        pad = self.padvalue
+        final_pred = torch.zeros([1, self.num_classes, ori_height, ori_width], dtype=self._acc_dtype(x), device=x.device)
+        for scale in self.scales:
+            height, width, rows, cols = self._plan(scale, ori_height, ori_width)
+            if fused and self._fused_view(x, final_pred, (height, width), [r[0] for r in rows], [c[0] for c in cols], crop, pad, True):
+                continue
+            # cv2.resize(INTER_LINEAR) of a float image: half-pixel bilinear without antialiasing
+            new_img = F.interpolate(x, size=[height, width], mode='bilinear', align_corners=False)
+            if max(height, width) <= min(crop):
+                new_img = ops_slide.pad_to(new_img, crop, pad)
+                preds = self.inference(new_img, flip=True)[:, :, 0:height, 0:width]
+            else:
+                if height < crop[0] or width < crop[1]:
+                    new_img = ops_slide.pad_to(new_img, crop, pad)
+                new_h, new_w = int(new_img.shape[2]), int(new_img.shape[3])
+                preds = torch.zeros([1, self.num_classes, new_h, new_w], dtype=final_pred.dtype, device=x.device)
+                count = torch.zeros([1, 1, new_h, new_w], dtype=final_pred.dtype, device=x.device)
+                for h0, h1 in rows:
+                    for w0, w1 in cols:
+                        crop_img = new_img[:, :, h0:h1, w0:w1]
+                        if h1 == new_h or w1 == new_w:
+                            crop_img = ops_slide.pad_to(crop_img, crop, pad)
+                        pred = self.inference(crop_img, flip=True)
+                        preds[:, :, h0:h1, w0:w1] += pred[:, :, 0:h1 - h0, 0:w1 - w0]
+                        count[:, :, h0:h1, w0:w1] += 1
+                preds = preds / count
+                preds = preds[:, :, :height, :width]
+            preds = F.interpolate(preds, (ori_height, ori_width), mode='bilinear', align_corners=self.align_corners)
+            final_pred += preds
+        return final_pred
+
+
+class TTAWrapperSlide(_EqualWindows):
+    def __init__(self, model, scale_list, flip=True, strides=None, crop_size=None, *, num_classes=150, img_scale=(2048, 512)):
+        super().__init__(model, scale_list, flip)
+        self.num_classes = num_classes
+        self.crop_size = crop_size if crop_size else [512, 512]
+        self.strides = strides if strides else self.crop_size      # defaults to non-overlapping windows
+        self.base_size = 512
+        self.img_scale = img_scale
+        printlog(f'Sliding window : strides : {self.strides} crop_size {self.crop_size} image_scales: {self.image_scales}')
+
+    @property
+    def image_flips(self):
+        return [f for _ in self.scales for f in ((True, False) if self.flip else (False,))]
+
+    @property
+    def image_scales(self):
+        """((height, width), scale) of every view: ``img_scale`` is read as (height, width) as the reference reads it"""
+        return [((int(self.img_scale[0] * s), int(self.img_scale[1] * s)), s) for s in self.scales
+                for _ in ((True, False) if self.flip else (False,))]
+
+    def _plan(self, shape, scale):
+        new_h, new_w = shape
+        rows = ops_tta.windows_1d(new_h, int(self.crop_size[0]), int(self.strides[0])) if new_h >= 1 else []
+        cols = ops_tta.windows_1d(new_w, int(self.crop_size[1]), int(self.strides[1])) if new_w >= 1 else []
+        if len(rows) < 1 or len(cols) < 1:
+            raise ValueError(f'TTAWrapperSlide: scale {scale} gives a {new_h} x {new_w} image with {len(rows)} x {len(cols)} windows '
+                             f'of crop {list(self.crop_size)} and strides {list(self.strides)}: the window count would be zero')
+        return rows, cols
+
+    def forward(self, x):
+        x = self._input(x)
+        batch, _, ori_height, ori_width = x.size()
+        assert batch == 1, "only supporting batchsize 1."
+        fused = ops_slide.hip_applies(x)
+        final_pred = torch.zeros([1, self.num_classes, ori_height, ori_width], dtype=self._acc_dtype(x), device=x.device)
+        for flip, ((new_h, new_w), scale) in zip(self.image_flips, self.image_scales):
+            rows, cols = self._plan((new_h, new_w), scale)
+            win = (rows[0][1] - rows[0][0], cols[0][1] - cols[0][0])        # every window of a view has this size
+            if fused and x.shape[1] <= 8 and self._fused_view(x, final_pred, (new_h, new_w), [r[0] for r in rows], [c[0] for c in cols],
+                                                               win, [0.0] * x.shape[1], flip):
+                continue
+            new_img = F.interpolate(x, size=[new_h, new_w], mode='bilinear', align_corners=False)
+            preds = torch.zeros([1, self.num_classes, new_h, new_w], dtype=final_pred.dtype, device=x.device)
+            count = torch.zeros([1, 1, new_h, new_w], dtype=final_pred.dtype, device=x.device)
+            for h0, h1 in rows:
+                for w0, w1 in cols:
+                    pred = self.inference(new_img[:, :, h0:h1, w0:w1], flip=flip)
+                    preds[:, :, h0:h1, w0:w1] += pred[:, :, 0:h1 - h0, 0:w1 - w0]
+                    count[:, :, h0:h1, w0:w1] += 1
+            preds = preds / count
             preds = F.interpolate(preds, (ori_height, ori_width), mode='bilinear', align_corners=self.align_corners)
             final_pred += preds
         return final_pred

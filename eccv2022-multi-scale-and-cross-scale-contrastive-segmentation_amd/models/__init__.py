@@ -5,4 +5,4 @@ from .Swin import SwinTransformer
 from .OCR import OCRNet, SpatialGatherModule, ObjectAttentionBlock2D, SpatialOCR_Module
 from .ResNet import resnet50, resnet101
 from .DeepLabv3 import DeepLabv3, ASPP
-from .TTA import TTAWrapper, TTAWrapperCTS
+from .TTA import TTAWrapper, TTAWrapperCTS, TTAWrapperPC, TTAWrapperSlide
