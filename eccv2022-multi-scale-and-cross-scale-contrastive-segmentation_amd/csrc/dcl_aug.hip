@@ -15,19 +15,12 @@
 #include <stdint.h>
 
 #include "dcl_aug_plan.h"
+#include "dcl_colour.h"
 
 namespace {
 
 constexpr int NTHR = 256;
 constexpr int NSEL = 1024;          // threads of a candidate's workgroup
-
-struct Rgb {
-    float r, g, b;
-};
-
-__device__ __forceinline__ float clamp255(float v) { return fminf(fmaxf(v, 0.f), 255.f); }
-
-__device__ __forceinline__ float luma(const Rgb v) { return (299.f * v.r + 587.f * v.g + 114.f * v.b) / 1000.f; }
 
 // the resized image at (ry, rx): sum over row taps of wy * (sum over column taps of wx * src)
 __device__ __forceinline__ Rgb resized_pixel(const uint8_t *__restrict__ img, const dau_plan &pl, const DauAxis ay, const DauAxis ax,
@@ -54,67 +47,6 @@ __device__ __forceinline__ Rgb resized_pixel(const uint8_t *__restrict__ img, co
         acc.b = fmaf(wy, line.b, acc.b);
     }
     return acc;
-}
-
-// RGB -> HSV -> RGB with the hue turned by delta; v stays in [0, 255], s and h are ratios
-__device__ __forceinline__ Rgb hue_shift(const Rgb v, float delta)
-{
-    const float maxc = fmaxf(v.r, fmaxf(v.g, v.b)), minc = fminf(v.r, fminf(v.g, v.b));
-    const bool eq = maxc == minc;
-    const float cr = maxc - minc;
-    const float s = cr / (eq ? 1.f : maxc);
-    const float d = eq ? 1.f : cr;
-    const float rc = (maxc - v.r) / d, gc = (maxc - v.g) / d, bc = (maxc - v.b) / d;
-    float h;
-    if (maxc == v.r)
-        h = bc - gc;
-    else if (maxc == v.g)
-        h = 2.f + rc - bc;
-    else
-        h = 4.f + gc - rc;
-    h = h / 6.f + 1.f;
-    h = h - floorf(h);
-    h = h + delta;
-    h = h - floorf(h);
-    const float h6 = h * 6.f;
-    const float fl = floorf(h6);
-    const float f = h6 - fl;
-    const int i = ((int)fl) % 6;
-    const float p = clamp255(maxc * (1.f - s));
-    const float q = clamp255(maxc * (1.f - f * s));
-    const float t = clamp255(maxc * (1.f - (1.f - f) * s));
-    switch (i) {
-    case 0: return {maxc, t, p};
-    case 1: return {q, maxc, p};
-    case 2: return {p, maxc, t};
-    case 3: return {p, q, maxc};
-    case 4: return {t, p, maxc};
-    default: return {maxc, p, q};
-    }
-}
-
-// operations [first, last) of the plan's chain
-__device__ __forceinline__ Rgb colour_ops(Rgb v, const dau_plan &pl, int first, int last, float m)
-{
-    for (int i = first; i < last; ++i) {
-        switch (pl.perm[i]) {
-        case 0:
-            v = {clamp255(pl.b * v.r), clamp255(pl.b * v.g), clamp255(pl.b * v.b)};
-            break;
-        case 1:
-            v = {clamp255(m + pl.c * (v.r - m)), clamp255(m + pl.c * (v.g - m)), clamp255(m + pl.c * (v.b - m))};
-            break;
-        case 2: {
-            const float L = luma(v);
-            v = {clamp255(L + pl.s * (v.r - L)), clamp255(L + pl.s * (v.g - L)), clamp255(L + pl.s * (v.b - L))};
-            break;
-        }
-        default:
-            v = hue_shift(v, pl.delta);
-            break;
-        }
-    }
-    return v;
 }
 
 __global__ __launch_bounds__(NSEL) void k_aug_crop_select(const uint8_t *__restrict__ lbl, const uint8_t *__restrict__ lut,

@@ -5,7 +5,12 @@ augmentation") and include/dcl_aug.h: flip, resize, pad, crop, colour, normalise
 Three parts: ``AugmentPlanner`` draws a sample's ``Plan`` (every random quantity of the chain) on the host from a counter-based
 stream, ``apply_plan_torch`` is the torch composition of the arithmetic (CPU tensors, unsupported plans, ``DCL_AUG_HIP=0``; the
 oracle of the kernels), ``DeviceAugment`` turns lists of decoded uint8 tensors and plans into the batch, on libdcl_aug.so where
-the plan is supported."""
+the plan is supported.
+
+``planner_for`` is what the manager calls: ``ChainPlanner`` adds the keys 'blur', 'pad' and 'resize' (BlurPIL, PadNP, Resize) and
+experiments without an ignore class (CaDIS experiment 1).  What those keys do after the crop is the plan's ``chain``, which
+``apply_plan_torch`` composes in torch and ``DeviceAugment`` runs on libdcl_blur.so (include/dcl_blur.h); a plan without a chain
+takes the path above, untouched."""
 import math
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
@@ -45,6 +50,18 @@ class Plan:
     normalise: bool = True
     ignore: int = 255
     max_ratio: Optional[float] = None
+    # what follows the crop on the image's planes, in the order of the config's list: ('pad', top, bottom), ('blur', R), ('colour',).
+    # Empty: perm runs right after the crop (dau_apply).  Otherwise perm runs where the ('colour',) item stands, and only there.
+    chain: tuple = ()
+
+    @property
+    def out_h(self) -> int:
+        """Rows of the sample's slice of the batch: the crop's and those the chain's pads add."""
+        return self.h + sum(it[1] + it[2] for it in self.chain if it[0] == 'pad')
+
+    @property
+    def out_w(self) -> int:
+        return self.w
 
 
 def network_lut(dataset, experiment) -> torch.Tensor:
@@ -73,14 +90,21 @@ class AugmentPlanner:
         tv = dict(transform_values or {})
         for t in transforms:
             if t in UNSUPPORTED:
-                raise ValueError(f"transform {t} is not available on the device augmentation path (DESIGN.md, 'Input augmentation')")
+                raise ValueError(f"transform {t} is not available to AugmentPlanner: planner_for() returns the planner that takes it "
+                                 "(DESIGN.md, 'Input augmentation')")
             if t not in ACCEPTED:
                 raise ValueError(f'transform {t} not recognized')
+        ignore = ignore_id(dataset, experiment)
+        if ignore < 0:
+            raise ValueError(f'{dataset} experiment {experiment} has no ignore class to pad labels with')
+        self._setup(transforms, tv, dataset, experiment, seed, ignore)
+
+    def _setup(self, transforms, tv, dataset, experiment, seed, ignore):
+        """The keys of ACCEPTED (shared with ChainPlanner, which has taken its own keys out of the list)."""
         self.transforms, self.values = list(transforms), tv
         self.dataset, self.experiment, self.seed = dataset, experiment, int(seed)
-        self.ignore = ignore_id(dataset, experiment)
-        if self.ignore < 0:
-            raise ValueError(f'{dataset} experiment {experiment} has no ignore class to pad labels with')
+        self.ignore = ignore
+        self.resize = None                          # ChainPlanner's 'resize' key: (target (h, w) or None, min side or None)
         self.flip = 'flip' in transforms
         self.random_scale = 'random_scale' in transforms
         self.random_crop = 'RandomCropImgLbl' in transforms
@@ -102,7 +126,9 @@ class AugmentPlanner:
             self.min_side, self.fit_stride = tv['min_side_length'], tv.get('fit_stride_val')
 
     def plan(self, H, W, epoch=0, index=0) -> Plan:
-        rng = np.random.default_rng((self.seed, int(epoch), int(index)))
+        return self._draw(np.random.default_rng((self.seed, int(epoch), int(index))), H, W)
+
+    def _draw(self, rng, H, W) -> Plan:
         # every quantity is drawn, in this order, whether or not it is used: a key of the list never shifts another's draw
         u_flip, u_scale = rng.random(), rng.random()
         scale, aspect = rng.uniform(*self.scale_range), rng.uniform(*self.aspect_range)
@@ -117,13 +143,15 @@ class AugmentPlanner:
 
         rh, rw = H, W
         resized = self.random_scale and u_scale < self.p_random_scale
-        if self.resize_val:
+        if self.resize is not None and self.resize[0] is not None:
+            rh, rw = self.resize[0]
+        elif self.resize_val or self.resize is not None:
             ratio = self.min_side / min(W, H)
             rw, rh = int(round(W * ratio)), int(round(H * ratio))
         elif resized:
             rw, rh = int(W * (math.sqrt(aspect) * scale)), int(H * (math.sqrt(1.0 / aspect) * scale))
         Hc, Wc, pt, pl = rh, rw, 0, 0
-        if self.resize_val and self.fit_stride:
+        if (self.resize_val or self.resize is not None) and self.fit_stride:
             Hc, Wc = -(-rh // self.fit_stride) * self.fit_stride, -(-rw // self.fit_stride) * self.fit_stride
         elif resized:                               # (the reference pads only inside the branch that resized)
             ch, cw = self.crop_shape
@@ -144,6 +172,71 @@ class AugmentPlanner:
         return Plan(H=H, W=W, rh=rh, rw=rw, Hc=Hc, Wc=Wc, pt=pt, pl=pl, h=h, w=w, flip=self.flip and u_flip < 0.5, corners=corners,
                     perm=ops, b=b, c=c, s=s, delta=delta, normalise=self.normalise, ignore=self.ignore,
                     max_ratio=self.max_ratio if self.random_crop else None)
+
+
+BLUR_P, BLUR_KERNEL_LIMITS = 0.05, (3, 7)        # parse_transform_lists: BlurPIL(probability=.05, kernel_limits=(3, 7))
+PAD_ROWS = (2, 2)                               # ... PadNP(ver=(2, 2), hor=(0, 0), padding_mode='reflect'): 540 rows -> 544
+NO_IGNORE = 255                                 # Plan.ignore of an experiment without an ignore class: no lookup table produces it
+
+
+class ChainPlanner(AugmentPlanner):
+    """AugmentPlanner and the reference's remaining ``data.transforms`` keys: 'blur', 'pad' and 'resize'.  Its draws come after every
+    draw of AugmentPlanner on the same stream, so a list within ACCEPTED gives AugmentPlanner's plans; what the new keys add is the
+    plan's ``chain``.  An experiment without an ignore class is taken as long as nothing pads labels with it."""
+
+    def __init__(self, transforms, transform_values, dataset, experiment, seed=0):
+        tv = dict(transform_values or {})
+        for t in transforms:
+            if t not in ACCEPTED and t not in UNSUPPORTED:
+                raise ValueError(f'transform {t} not recognized')
+        ignore = ignore_id(dataset, experiment)
+        self._setup([t for t in transforms if t in ACCEPTED], tv, dataset, experiment, seed, ignore if ignore >= 0 else NO_IGNORE)
+        self.blur = 'blur' in transforms
+        self.blur_p = float(tv.get('blur_p', BLUR_P))
+        self.blur_limits = tuple(int(v) for v in tv.get('blur_kernel_limits', BLUR_KERNEL_LIMITS))
+        if self.blur and not self.blur_limits[0] < self.blur_limits[1]:
+            raise ValueError(f'blur: blur_kernel_limits {self.blur_limits} is an empty range')
+        if 'pad' in transforms and dataset != 'CADIS':
+            raise ValueError(f"transform pad is for CADIS only (PadNP(ver=(2, 2)) takes its 540 rows to 544), not for {dataset}")
+        self.pad = PAD_ROWS if 'pad' in transforms and 'crop' not in transforms else None
+        if 'resize' in transforms:
+            target, self.fit_stride = tv.get('target_size'), tv.get('fit_stride')
+            if target is None and tv.get('min_side_length') is None:
+                raise ValueError("transform resize needs transform_values.target_size [h, w] or transform_values.min_side_length")
+            self.resize = (tuple(int(v) for v in target) if target is not None else None, tv.get('min_side_length'))
+            self.min_side = tv.get('min_side_length')
+        if ignore < 0:
+            for key, pads in (('random_scale', self.random_scale), ('resize', self.resize is not None and bool(self.fit_stride)),
+                              ('resize_val', self.resize_val)):
+                if pads:
+                    raise ValueError(f'transform {key} pads labels with the ignore class, and {dataset} experiment {experiment} has none')
+        # the image's steps after the crop, in the order of the list (the later colour key wins, as in AugmentPlanner)
+        colour_key = 'pseudo_colorjitter' if 'pseudo_colorjitter' in transforms else 'colorjitter'
+        self.order = [t for t in transforms if t in ('pad', 'blur', colour_key)]
+
+    def plan(self, H, W, epoch=0, index=0) -> Plan:
+        rng = np.random.default_rng((self.seed, int(epoch), int(index)))
+        p = self._draw(rng, H, W)
+        u_blur = rng.random()                       # drawn whether or not the list holds 'blur', after every draw of _draw
+        R = int(rng.integers(*self.blur_limits))
+        chain = []
+        for t in self.order:
+            if t == 'pad' and self.pad is not None:
+                chain.append(('pad',) + self.pad)
+            elif t == 'blur' and self.blur and u_blur < self.blur_p:
+                chain.append(('blur', R))
+            elif t not in ('pad', 'blur') and p.perm:
+                chain.append(('colour',))
+        if chain != [('colour',)]:                  # colour alone: AugmentPlanner's plan, three launches
+            p.chain = tuple(chain)
+        return p
+
+
+def planner_for(transforms, transform_values, dataset, experiment, seed=0):
+    """The planner of a transform list: AugmentPlanner for what it takes (the same plans as ever), else ChainPlanner."""
+    if all(t in ACCEPTED for t in transforms) and ignore_id(dataset, experiment) >= 0:
+        return AugmentPlanner(transforms, transform_values, dataset, experiment, seed)
+    return ChainPlanner(transforms, transform_values, dataset, experiment, seed)
 
 
 # ---- the arithmetic, in torch ------------------------------------------------------------------------------------------------------
@@ -237,6 +330,60 @@ def hue(x, delta):
     return torch.gather(table, 0, i[None, ..., None].expand(1, *i.shape, 3))[0]
 
 
+def box_of(radius):
+    """(l, ww, fw) of PIL's GaussianBlur(radius): the extended box of its three passes an axis (csrc/dcl_blur_plan.h dbl_box_of
+    restated: the same double operations in the same order, the two weights rounded to fp32 last)."""
+    s2 = float(radius) * float(radius) / 3.0
+    L = math.sqrt(12.0 * s2 + 1.0)
+    l = math.floor((L - 1.0) / 2.0)
+    a = (2.0 * l + 1.0) * (l * (l + 1.0) - 3.0 * s2) / (6.0 * (s2 - (l + 1.0) * (l + 1.0)))
+    ww = 1.0 / (2.0 * (l + a) + 1.0)
+    return int(l), float(np.float32(ww)), float(np.float32((1.0 - (2.0 * l + 1.0) * ww) / 2.0))
+
+
+def box_pass(x, dim, l, ww, fw):
+    """One extended-box pass along ``dim``: ww (sum of the 2 l + 1 inner taps, from -l upwards) + fw (the two outer taps), every
+    index clamped to the axis."""
+    n = x.shape[dim]
+    idx = torch.arange(n, device=x.device)
+    tap = lambda d: x.index_select(dim, (idx + d).clamp(0, n - 1))
+    acc = torch.zeros_like(x)
+    for d in range(-l, l + 1):
+        acc = acc + tap(d)
+    return ww * acc + fw * (tap(-l - 1) + tap(l + 1))
+
+
+def gaussian_blur(x, radius):
+    """[h, w, ...] -> the same: three passes along the rows (x), then three along the columns (y)."""
+    l, ww, fw = box_of(radius)
+    for dim in (1, 1, 1, 0, 0, 0):
+        x = box_pass(x, dim, l, ww, fw)
+    return x
+
+
+def reflect_rows(x, top, bottom):
+    """numpy.pad(mode='reflect') along the rows of [h, ...]."""
+    h = x.shape[0]
+    assert 0 <= top <= h - 1 and 0 <= bottom <= h - 1, f'reflect padding {(top, bottom)} needs more than {h} rows'
+    r = torch.arange(-top, h + bottom, device=x.device).abs()
+    r = torch.where(r > h - 1, 2 * (h - 1) - r, r)
+    return x.index_select(0, r)
+
+
+def colour_chain(x, plan):
+    """plan.perm on [h, w, 3] values in [0, 255]."""
+    for op in plan.perm:
+        if op == BRIGHTNESS:
+            x = brightness(x, plan.b)
+        elif op == CONTRAST:
+            x = contrast(x, plan.c)
+        elif op == SATURATION:
+            x = saturation(x, plan.s)
+        else:
+            x = hue(x, plan.delta)
+    return x
+
+
 def candidate_verdict(window, ignore, max_ratio):
     """(acceptable, max_count, sum_count) of one candidate window of network labels."""
     cnt = torch.bincount(window.reshape(-1).to(torch.int64), minlength=256).cpu().numpy().astype(np.int64)
@@ -271,15 +418,19 @@ def apply_plan_torch(img_u8, lbl_u8, plan: Plan, lut, dtype=torch.float32):
     chosen = choose_crop(lcanvas, plan)
     i, j = plan.corners[chosen]
     x, y = canvas[i:i + plan.h, j:j + plan.w], lcanvas[i:i + plan.h, j:j + plan.w]
-    for op in plan.perm:
-        if op == BRIGHTNESS:
-            x = brightness(x, plan.b)
-        elif op == CONTRAST:
-            x = contrast(x, plan.c)
-        elif op == SATURATION:
-            x = saturation(x, plan.s)
-        else:
-            x = hue(x, plan.delta)
+    if not plan.chain:
+        x = colour_chain(x, plan)
+    else:                                           # the kernels' order: dau_apply leaves x / 255, dbl_from_unit takes it back
+        x = x / 255 * 255
+        for item in plan.chain:
+            if item[0] == 'pad':
+                x, y = reflect_rows(x, item[1], item[2]), reflect_rows(y, item[1], item[2])
+            elif item[0] == 'blur':
+                x = gaussian_blur(x, item[1])
+            elif item[0] == 'colour':
+                x = colour_chain(x, plan)
+            else:
+                raise ValueError(f'chain item {item} not recognized')
     x = x / 255
     if plan.normalise:
         x = (x - torch.tensor(MEAN, dtype=dtype, device=x.device)) / torch.tensor(STD, dtype=dtype, device=x.device)
@@ -289,7 +440,8 @@ def apply_plan_torch(img_u8, lbl_u8, plan: Plan, lut, dtype=torch.float32):
 class DeviceAugment:
     """Lists of decoded tensors and plans -> the batch (float32 [B, 3, h, w], int64 [B, h, w]) on the tensors' device and the
     CURRENT stream.  Per sample: the kernels of libdcl_aug.so (three launches, no host synchronisation) when the tensors are on
-    the GPU, the switch is on and ``dau_supported`` takes the plan; the composition otherwise."""
+    the GPU, the switch is on and ``dau_supported`` takes the plan; the composition otherwise.  A plan with a ``chain`` goes on
+    from there on libdcl_blur.so (``_chain``) when its switch is on too and ``dbl_supported`` takes every blur of the chain."""
 
     def __init__(self, lut):
         self.lut = lut.to(torch.uint8).contiguous()
@@ -310,13 +462,55 @@ class DeviceAugment:
                 and tuple(img.shape) == (plan.H, plan.W, 3) and tuple(lbl.shape) == (plan.H, plan.W)):
             return None
         from .. import _lib_aug as la
+        if plan.chain:
+            from dataclasses import replace
+            from .. import _lib_blur as lb
+            h = plan.h
+            for item in plan.chain:
+                if item[0] == 'pad':
+                    if not (0 <= item[1] <= h - 1 and 0 <= item[2] <= h - 1):
+                        return None
+                    h += item[1] + item[2]
+                elif item[0] == 'blur':
+                    if not lb.supported(3, h, plan.w, item[1]):
+                        return None
+                elif item[0] != 'colour':
+                    return None
+            if not dbg.blur_hip or 3 * h * plan.w >= 2 ** 31:
+                return None
+            plan = replace(plan, perm=(), normalise=False)      # dau_apply's part: up to the crop, x / 255
         cp = la.c_plan(plan)
         return cp if la.supported(cp) else None
 
+    def _chain(self, planes, lbl, plan, ws, out, out_l, st):
+        """What follows dau_apply for a plan with a chain: ``planes`` (float32 [3, h, w] of x / 255) and ``lbl`` (int64 [h, w]) ->
+        the sample's slices ``out`` / ``out_l``, every launch on the current stream."""
+        from .. import _lib_blur as lb
+        lb.from_unit(planes, planes, st)
+        pads = sum(item[0] == 'pad' for item in plan.chain)
+        for item in plan.chain:
+            if item[0] == 'pad':
+                pads -= 1
+                ho = planes.shape[1] + item[1] + item[2]
+                padded = torch.empty(3, ho, planes.shape[2], dtype=torch.float32, device=planes.device)
+                lbl_p = out_l if pads == 0 else torch.empty(ho, planes.shape[2], dtype=torch.int64, device=planes.device)
+                lb.pad_rows(planes, padded, lbl, lbl_p, item[1], item[2], st)
+                planes, lbl = padded, lbl_p
+            elif item[0] == 'blur':
+                dst, scratch = torch.empty_like(planes), torch.empty_like(planes)
+                lb.blur(planes, dst, scratch, item[1], st)
+                planes = dst
+            else:
+                cp = lb.colour_plan(plan, planes.shape[1], planes.shape[2])
+                if CONTRAST in plan.perm:
+                    lb.gray_mean(planes, cp, ws, st)
+                lb.colour(planes, cp, ws, st)
+        lb.normalise(planes, out, plan.normalise, st)
+
     def __call__(self, imgs, lbls, plans):
         assert len(imgs) == len(lbls) == len(plans) and len(imgs) > 0
-        h, w = plans[0].h, plans[0].w
-        assert all((p.h, p.w) == (h, w) for p in plans), 'every plan of a batch must have the same crop size'
+        h, w = plans[0].out_h, plans[0].out_w
+        assert all((p.out_h, p.out_w) == (h, w) for p in plans), 'every plan of a batch must have the same crop size'
         dev = imgs[0].device
         B = len(imgs)
         out = torch.empty(B, 3, h, w, dtype=torch.float32, device=dev)
@@ -337,8 +531,15 @@ class DeviceAugment:
                 continue
             if cp.P > 1:
                 la.crop_select(lbl, lut, cp, ws[n], st)
-            if CONTRAST in plan.perm:
+            if CONTRAST in plan.perm and not plan.chain:
                 la.gray_mean(img, cp, ws[n], st)
+            if plan.chain:
+                planes = torch.empty(3, plan.h, plan.w, dtype=torch.float32, device=dev)
+                padded = any(item[0] == 'pad' for item in plan.chain)
+                y = torch.empty(plan.h, plan.w, dtype=torch.int64, device=dev) if padded else out_l[n]
+                la.apply(img, lbl, lut, cp, ws[n], planes, y, st)
+                self._chain(planes, y, plan, ws[n], out[n], out_l[n], st)
+                continue
             la.apply(img, lbl, lut, cp, ws[n], out[n], out_l[n], st)
         self.last_ws = ws
         return out, out_l

@@ -116,6 +116,66 @@ class PascalC(_Raw):
         assert len(labels) == len(self.targets), f'{targets_dir}: {len(labels)} labels for {len(self.images)} images'
 
 
+def read_frame_table(path):
+    """The rows of a CaDIS frame table (the reference's data/data.csv) as dicts of strings, in the file's order."""
+    import csv
+    if not os.path.exists(path):
+        raise FileNotFoundError(f'{path}: the CaDIS frame table (config key data.frame_table) not found')
+    with open(path, newline='') as f:
+        rows = list(csv.DictReader(f))
+    for column in ('img_path', 'lbl_path', 'vid_num'):
+        if not rows or column not in rows[0]:
+            raise KeyError(f'{path}: the frame table has no column {column}')
+    return rows
+
+
+def _is_one(row, column):
+    """pandas' ``df[column] == 1`` on a row of strings: an empty cell, or a table without the column, is not 1."""
+    v = row.get(column)
+    return v not in (None, '') and float(v) == 1
+
+
+class CaDIS(_Raw):
+    """The frames of a CaDIS frame table, filtered as the reference's datasets/CaDIS.py get_cadis_dataframes does: ``subset``
+    'train' keeps the frames of the train videos of ``DATA_SPLITS[split]``, 'valid' those of the validation videos that are not
+    propagated; ``use_relabeled`` reads ``relabeled/<name>`` for relabeled frames (and takes them off the blacklist), ``blacklist``
+    drops blacklisted frames.  With a three-way split, ``mode`` 'inference' validates on the test videos.  Paths are split on '\\',
+    joined under ``root`` and decoded to raw ids; ``rows`` are the kept rows, ``self.rows[i]`` belongs to item i.
+
+    Stated deviations: a table without a ``propagated`` column counts every frame as not propagated (the shipped table has none;
+    the reference raises KeyError there); the reference tests ``mode`` for 'infer', which nothing sets."""
+    dataset = 'CADIS'
+
+    def __init__(self, root, frames, split=1, experiment=2, planner=None, mode='training', subset='train', use_relabeled=False,
+                 blacklist=True):
+        super().__init__(planner)
+        from ..utils import DATASETS_INFO
+        assert subset in ('train', 'valid'), f'subset {subset} is not valid'
+        self.root, self.split, self.experiment, self.subset = root, int(split), experiment, subset
+        rows = read_frame_table(frames) if isinstance(frames, (str, os.PathLike)) else list(frames)
+        for column in ('img_path', 'lbl_path', 'vid_num'):
+            if not rows or column not in rows[0]:
+                raise KeyError(f'the frame table has no column {column}')
+        splits = DATASETS_INFO['CADIS'].DATA_SPLITS[self.split]
+        if len(splits) not in (2, 3):
+            raise ValueError('splits must be a list of length 2 or 3')
+        videos = splits[0] if subset == 'train' else splits[2] if len(splits) == 3 and mode == 'inference' else splits[1]
+        rows = [dict(r) for r in rows if int(float(r['vid_num'])) in videos and not (subset == 'valid' and _is_one(r, 'propagated'))]
+        if use_relabeled:
+            for r in rows:
+                if _is_one(r, 'relabeled'):
+                    r['blacklisted'] = '0'
+                    r['lbl_path'] = 'relabeled/' + r['lbl_path'].replace('\\', '/').split('/')[-1]
+        if blacklist:
+            rows = [r for r in rows if not _is_one(r, 'blacklisted')]
+        self.rows = rows
+        self.images = [os.path.join(root, *r['img_path'].split('\\')) for r in rows]
+        self.targets = [os.path.join(root, *r['lbl_path'].split('\\')) for r in rows]
+        for path in self.images + self.targets:
+            if not os.path.exists(path):
+                raise FileNotFoundError(f'{path} (a frame of the CaDIS frame table) not found')
+
+
 class SyntheticRaw(_Raw):
     """uint8 images and blocky uint8 labels in the RAW ids of ``dataset`` (the ids its lookup table maps to a class, and the first
     unmapped one for the ignore class), without touching disk."""

@@ -223,13 +223,13 @@ class BaseManager:
     def _load_raw_data(self):
         """The raw input path (datasets/raw.py, datasets/augment.py): the loaders only decode files (or draw ``synthetic_raw``
         pixels) and attach each sample's augmentation plan; ``_upload`` runs the augmentation on the device."""
-        from ..datasets import ADE20K, AugmentPlanner, Cityscapes, DeviceAugment, PascalC, SyntheticRaw, list_collate, network_lut
+        from ..datasets import ADE20K, Cityscapes, DeviceAugment, PascalC, SyntheticRaw, list_collate, network_lut, planner_for
         dcfg, seed = self.config['data'], self.config['seed']
         tv = dcfg.get('transform_values', {})
-        plan_t = AugmentPlanner(dcfg.get('transforms', ['RandomCropImgLbl', 'torchvision_normalise']), tv, self.dataset,
-                                self.experiment, seed)
-        plan_v = AugmentPlanner(dcfg.get('transforms_val', ['torchvision_normalise']), dcfg.get('transform_values_val', tv),
-                                self.dataset, self.experiment, seed + 1)
+        plan_t = planner_for(dcfg.get('transforms', ['RandomCropImgLbl', 'torchvision_normalise']), tv, self.dataset,
+                             self.experiment, seed)
+        plan_v = planner_for(dcfg.get('transforms_val', ['torchvision_normalise']), dcfg.get('transform_values_val', tv),
+                             self.dataset, self.experiment, seed + 1)
         if plan_v.resize_val and self.dataset not in self.ORIGINAL_SIZE_DATASETS:
             printlog("[mscs_amd] transforms_val holds resize_val: validate() will raise (the reference's original-label "
                      f"evaluation applies to {' and '.join(self.ORIGINAL_SIZE_DATASETS)} only)")
@@ -252,8 +252,10 @@ class BaseManager:
             elif self.dataset == 'PASCALC':
                 split = dcfg.get('split', ['train', 'val'])
                 train, valid = PascalC(root, split[0], plan_t), PascalC(root, split[1], plan_v)
+            elif self.dataset == 'CADIS':
+                train, valid = self._cadis_readers(root, plan_t, plan_v)
             else:
-                raise NotImplementedError(f"no reader for dataset {self.dataset}: CITYSCAPES, ADE20K and PASCALC are ported "
+                raise NotImplementedError(f"no reader for dataset {self.dataset}: CITYSCAPES, ADE20K, PASCALC and CADIS are ported "
                                           "(SURVEY.md row 15)")
         self._augment = DeviceAugment(network_lut(self.dataset, self.experiment))
         sampler = DistributedSampler(train, num_replicas=self.world_size, rank=self.rank) if self.parallel else None
@@ -264,6 +266,46 @@ class BaseManager:
         self.data_loaders['valid_loader'] = DataLoader(valid, batch_size=self.valid_batch_size, shuffle=False, num_workers=0,
                                                        collate_fn=list_collate)
         self.train_schedule = {e: 'train_loader' for e in range(self.config['train']['epochs'])}
+        self._schedule_repeat_factor(train)
+
+    def _cadis_readers(self, root, plan_t, plan_v):
+        """The CaDIS readers of the config (the reference's datasets/CaDIS.py get_cadis_dataframes): the frame table is
+        data.frame_table, else data/data.csv under the working directory (as the reference), else <data_path>/data.csv."""
+        from ..datasets import CaDIS, read_frame_table
+        dcfg = self.config['data']
+        if 'random_split' in dcfg:
+            raise NotImplementedError("data.random_split (the reference's legacy split of frames) is not ported: name the video "
+                                      "split with data.split")
+        table = dcfg.get('frame_table') or next((p for p in (os.path.join('data', 'data.csv'), os.path.join(root, 'data.csv'))
+                                                 if os.path.exists(p)), os.path.join(root, 'data.csv'))
+        rows = read_frame_table(table)
+        kw = dict(split=int(dcfg.get('split', 1)), experiment=self.experiment, mode=self.config.get('mode', 'training'),
+                  use_relabeled=dcfg.get('use_relabeled', False), blacklist=dcfg.get('blacklist', True))
+        return CaDIS(root, rows, planner=plan_t, subset='train', **kw), CaDIS(root, rows, planner=plan_v, subset='valid', **kw)
+
+    def _schedule_repeat_factor(self, train):
+        """data.repeat_factor [start, stop] (one number: until the last epoch): those epochs draw from train_repeat_factor_loader,
+        a BatchSampler(drop_last) over the repeat-factor sampler of the reader's rows (the reference's load_data schedule)."""
+        from ..datasets import list_collate
+        dcfg, epochs = self.config['data'], self.config['train']['epochs']
+        span = list(dcfg.get('repeat_factor') or [0, 0])
+        if len(span) == 1:
+            span.append(epochs)
+        scheduled = [e for e in range(*span) if e < epochs]
+        if not scheduled:
+            return
+        if not hasattr(train, 'rows'):
+            raise ValueError(f"data.repeat_factor needs the per-frame class columns of the CaDIS frame table; the {self.dataset} "
+                             "loader has none")
+        from ..utils.repeat_factor_sampling import RepeatFactorSampler
+        sampler = RepeatFactorSampler(train.rows, dcfg.get('repeat_factor_freq_thresh', 0.15), self.experiment, dataset=self.dataset,
+                                      num_replicas=self.world_size if self.parallel else 1, rank=self.rank if self.parallel else 0)
+        self.samplers['train_repeat_factor_loader'] = sampler
+        self.data_loaders['train_repeat_factor_loader'] = DataLoader(
+            train, batch_sampler=torch.utils.data.BatchSampler(sampler, batch_size=self.batch_size, drop_last=True),
+            num_workers=dcfg['num_workers'], pin_memory=self.device.type == 'cuda', collate_fn=list_collate)
+        for e in scheduled:
+            self.train_schedule[e] = 'train_repeat_factor_loader'
 
     def _param_groups(self):
         """``train.opt_keys`` {substring: {lr_mult, wd_mult}} -> optimizer parameter groups (reference:

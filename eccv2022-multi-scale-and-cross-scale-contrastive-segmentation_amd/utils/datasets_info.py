@@ -2,7 +2,8 @@
 with the same access pattern as the reference (utils/defaults.py:1, utils/datasets_info/*.py).
 The tables themselves are data (``datasets_info.json``, dumped by tools/gen_datasets_info.py);
 ``names`` is an id -> class-name dict whose length is ``num_all_classes`` and whose key 255 marks
-the ignore class."""
+the ignore class.  ``DATASETS_INFO['CADIS'].DATA_SPLITS`` is the reference's table of video splits
+(``datasets_splits.json``)."""
 import json
 import os
 
@@ -35,6 +36,10 @@ def _load():
         ci = [[_restore(p) for p in exp] for exp in class_info]
         names = [[exp[1][k] for k in sorted(exp[1].keys())] for exp in ci]
         info[ds] = _Info(CLASS_INFO=ci, CLASS_NAMES=names)
+    # DATA_SPLITS[split] = [train videos, validation videos(, test videos)] of the datasets that are split by video (CaDIS)
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "datasets_splits.json")) as f:
+        for ds, splits in json.load(f).items():
+            info[ds]["DATA_SPLITS"] = splits
     return info
 
 
