@@ -72,6 +72,7 @@ class DebugConfig:
     tsne_hip: bool = field(default_factory=lambda: _flag('DCL_TSNE_HIP'))                       # demo_tsne's exact t-SNE on libdcl_tsne.so; 0 = PyTorch
     slide_hip: bool = field(default_factory=lambda: _flag('DCL_SLIDE_HIP'))                     # TTAWrapperPC / TTAWrapperSlide on libdcl_slide.so; 0 = PyTorch
     blur_hip: bool = field(default_factory=lambda: _flag('DCL_BLUR_HIP'))                       # blur / pad / colour on planes on libdcl_blur.so; 0 = PyTorch
+    ohem_hip: bool = field(default_factory=lambda: _flag('DCL_OHEM_HIP'))                       # OhemCrossEntropy's mining on libdcl_ohem.so; 0 = PyTorch
     # ---- kernel variants set on the library at load (include/dcl_hip.h "tuning hook" entries)
     wgrad_variant: Optional[int] = field(default_factory=lambda: _int('DCL_WGRAD_VARIANT'))
     wgrad_wg_target: Optional[int] = field(default_factory=lambda: _int('DCL_WGRAD_TARGET'))    # workgroups a weight-gradient launch aims at

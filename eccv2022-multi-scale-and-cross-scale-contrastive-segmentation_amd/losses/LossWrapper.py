@@ -75,7 +75,7 @@ class LossWrapper(nn.Module):
         loss_list = list(self.loss_weightings.keys()) if loss_list is None else loss_list
         lazy = prediction if hasattr(prediction, 'materialize') else None     # models.ops.UpsampledLogits
         if lazy is not None and any(k not in ('CrossEntropyLoss', 'DenseContrastiveLossV2', 'DenseContrastiveLossV2_ms',
-                                              'TwoScaleLoss')
+                                              'TwoScaleLoss', 'OhemCrossEntropy')
                                     for k in self.loss_weightings if k in loss_list):
             prediction = lazy.materialize()           # a component without a fused path wants the full tensor
         for loss_class in self.loss_weightings:
@@ -99,6 +99,9 @@ class LossWrapper(nn.Module):
                         and fn.reduction == 'mean' and fn.label_smoothing == 0.0:
                     # bilinear up-sampling + weighted CE in one kernel, no full-resolution logits (csrc/dcl_upce.hip)
                     loss = lazy.cross_entropy(labels, weight=fn.weight, ignore_index=fn.ignore_index)
+                elif loss_class == 'OhemCrossEntropy' and lazy is not None:
+                    # hard-pixel mining on the low-resolution logits (csrc/dcl_ohem.hip): the module takes the lazy object
+                    loss = fn(lazy, labels)
                 elif loss_class in ('CrossEntropyLoss', 'OhemCrossEntropy'):
                     loss = fn(prediction if lazy is None else lazy.materialize(), labels)
                 else:

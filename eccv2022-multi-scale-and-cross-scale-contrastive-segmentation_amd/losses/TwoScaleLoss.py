@@ -55,10 +55,14 @@ class TwoScaleLoss(nn.Module):
     @staticmethod
     def _apply(fn, logits, target):
         """``fn(logits, target)``; logits kept at low resolution (models.ops.UpsampledLogits) go through the fused
-        up-sampling + cross-entropy kernel when fn is a plain mean-reduced nn.CrossEntropyLoss, else are materialised."""
+        up-sampling + cross-entropy kernel when fn is a plain mean-reduced nn.CrossEntropyLoss, are handed as they are to an
+        OhemCrossEntropy (which mines on them), else are materialised."""
         if hasattr(logits, 'materialize'):
             if type(fn) is nn.CrossEntropyLoss and fn.reduction == 'mean' and fn.label_smoothing == 0.0:
                 return logits.cross_entropy(target, weight=fn.weight, ignore_index=fn.ignore_index)
+            from .OhemCrossEntropy import OhemCrossEntropy
+            if isinstance(fn, OhemCrossEntropy):          # mines on the low-resolution logits (csrc/dcl_ohem.hip)
+                return fn(logits, target)
             logits = logits.materialize()
         return fn(logits, target)
 

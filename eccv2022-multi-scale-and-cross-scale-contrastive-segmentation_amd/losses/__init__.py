@@ -4,4 +4,5 @@ from .LovaszSoftmax import LovaszSoftmax
 from .DenseContrastiveLossV2 import DenseContrastiveLossV2
 from .DenseContrastiveLossV2_ms import DenseContrastiveLossV2_ms
 from .TwoScaleLoss import TwoScaleLoss
+from .OhemCrossEntropy import OhemCrossEntropy
 from .LossWrapper import LossWrapper

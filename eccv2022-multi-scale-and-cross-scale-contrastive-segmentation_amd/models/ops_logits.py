@@ -79,3 +79,15 @@ class UpsampledLogits:
                                  self.size[0], self.size[1], self.align_corners, holder)
         self.pred = holder["pred"]
         return loss
+
+    def ohem_cross_entropy(self, target, weight=None, ignore_index=-1, thresh=0.7, min_kept=100000):
+        """losses.OhemCrossEntropy (hard-pixel mining: the pixels whose target probability is below max(thresh, the min_kept-th
+        smallest)) of materialize() without materialising (csrc/dcl_ohem.hip between the two kernels of cross_entropy())."""
+        from ..losses.OhemCrossEntropy import hip_applies, ohem_cross_entropy
+        if not hip_applies(self.lowres, target, self.size):
+            return ohem_cross_entropy(self.materialize(), target, weight, ignore_index, thresh, min_kept)
+        holder = {}
+        loss = ohem_cross_entropy(self.lowres, target, weight, ignore_index, thresh, min_kept, size=self.size,
+                                  align_corners=self.align_corners, holder=holder)
+        self.pred = holder["pred"]
+        return loss
