@@ -26,6 +26,7 @@
 // The same kernel computes the data gradient: dx = conv3x3(dy, w') with w'[ci, co, ky, kx] = w[co, ci, 2-ky, 2-kx]
 // (k_pack_w3x3 with `transposed`).
 #include "dcl_conv_body.h"
+#include "dcl_conv_plan.h"
 
 namespace {
 
@@ -561,12 +562,7 @@ template <int R, int P, int S>
 static int launch_conv(const ConvArgs &a0, hipStream_t stream)
 {
     ConvArgs a = a0;
-    // (phases: tiles over one parity class of the output, ceil(Ho / 2) x ceil(Wo / 2) pixels, four classes per tile)
-    a.tiles_x = ((a.phases ? (a.Wo + 1) / 2 : a.Wo) + TW - 1) / TW;
-    a.tiles_y = ((a.phases ? (a.Ho + 1) / 2 : a.Ho) + 4 * P - 1) / (4 * P);
-    const int mtiles = (a.Cout + 31) / 32;
-    a.groups = (mtiles + R - 1) / R;
-    dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.N * a.groups * (a.phases == 1 ? 4 : 1)));
+    dim3 grid(conv_fill_grid(a, R, P));
     if (a.pre_sc) {
         // the producer norm's map + ReLU inside the patch staging (dcl_conv3x3_pre.hip): interleaved tiles only
         const bool ws2 = S == 1 && R == 2 && P == 2;
@@ -643,10 +639,7 @@ static int launch_conv(const ConvArgs &a0, hipStream_t stream)
 
 static int g_up2_phases = 2;    // in_up = 2: 2 = all four output parity classes of a tile in one workgroup (k_conv3x3_pm), 1 = one class
                                 // per workgroup (k_conv3x3_phases), 0 = zero-inserted input
-static int g_conv_min_wgs = 96;         // automatic tile: fewest workgroups a launch may have before the rows per wave are halved.
-// 192 (one round of 256 CUs three quarters full) until round 4; 96 since: the 192 / 384-channel branch convolutions then run as 96
-// workgroups with twice the rows per wave -- 22-33 % less CU-time per launch at 55 % more latency -- and leave the rest of the chip to
-// the other branches' kernels: step 90.7 -> 89.7 ms over three alternating pairs (profiles/r04_ab_conv_min_wgs.json)
+static int g_conv_min_wgs = DCL_CONV_MIN_WGS;   // automatic tile: fewest workgroups of a launch (dcl_conv_plan.h; tuning hook below)
 
 // ---- stem: 3x3 / stride 2 / pad 1 convolution with <= 4 input channels (reference models/HRNet.py:404-405: conv1 = 3 -> 64 on the
 // image), plain fp32 FMAs.  The tile kernels pad the contraction to a 16-channel chunk -- 5x the multiply-adds for 3 channels, each of
@@ -974,53 +967,11 @@ extern "C" int dcl_conv3x3_pre_supported(int N, int Cin, int Cout, int H, int W,
     return dcl_conv_pre_has_tile(R, P, stride, ws2) ? 1 : 0;
 }
 
+// the automatic tile (dcl_conv_plan.h) under this library's tuning switch
 static void auto_tile(int N, int Cout, int Ho, int Wo, int nchunk, int stride, int phases, int onetap, int tile_r, int tile_p,
                       int &R, int &P)
 {
-    const int mtiles = (Cout + 31) / 32;
-    if (phases == 2) {
-        // merged parity classes: 4 R P accumulator tiles per wave, at most 12 (16 spill) -- (3, 1), (2, 1), (1, 2 | 1); tiles run
-        // over the STORED gradient, ceil(Ho / 2) x ceil(Wo / 2)
-        R = mtiles % 3 == 0 ? 3 : (mtiles == 1 ? 1 : 2);
-        P = R == 1 ? 2 : 1;
-        auto wgs = [&](int p) {
-            return (long)(((Wo + 1) / 2 + TW - 1) / TW) * (((Ho + 1) / 2 + 4 * p - 1) / (4 * p)) * N * ((mtiles + R - 1) / R);
-        };
-        while (P > 1 && wgs(P) < g_conv_min_wgs)
-            P >>= 1;
-        if (tile_r > 0 && tile_p > 0 && 4 * tile_r * tile_p <= 12)
-            R = tile_r, P = tile_p;
-        return;
-    }
-    R = tile_r, P = tile_p;
-    if (stride == 2)
-        P = 1;
-    if (R <= 0 || P <= 0 || (stride == 2 && tile_r <= 0)) {
-        // measured on the four BasicBlock shapes of HRNet-W48 at batch 12 (tools/bench_conv3x3.py --tiles):
-        // channel tiles per wave in threes when that leaves no padded tile, else pairs; the most rows per wave
-        // that still give ~one workgroup per CU; tiny images fall back to single-tile waves to get enough
-        // workgroups.
-        R = (mtiles % 3 == 0 || mtiles >= 20) ? 3 : (mtiles == 1 ? 1 : 2);     // >= 20 tiles: one padded tile is < 5 %
-        if (mtiles == 5 && stride == 1 && !onetap)
-            R = 3;      // five tiles pad to six either way, and the (3, P) wave runs 324 P / 4 MFMAs per staged chunk against 216:
-                        // the head's 720 -> 144 data gradient (45 chunks), (2, 4) tile 4.17 ms = 0.21 of the roofline
-        auto wgs = [&](int r, int p) {
-            if (phases)
-                return (long)(((Wo + 1) / 2 + TW - 1) / TW) * (((Ho + 1) / 2 + 4 * p - 1) / (4 * p)) * N *
-                       ((mtiles + r - 1) / r) * 4;
-            return (long)((Wo + TW - 1) / TW) * ((Ho + 4 * p - 1) / (4 * p)) * N * ((mtiles + r - 1) / r);
-        };
-        P = stride == 2 ? 1 : 4;
-        while (P > 1 && wgs(R, P) < g_conv_min_wgs)
-            P >>= 1;
-        if (R == 2 && P == 4 && stride == 1 && !phases && nchunk <= 4)
-            P = 2;              // the (2, 2) tile runs two workgroups per CU (k_conv3x3_o2): 81 vs 100 us at 48 channels;
-                                // a short K loop is mostly prologue / epilogue, which two co-resident workgroups
-                                // hide.  With a long one (the 512-channel decoder convolutions of UPerNet) the (2, 4)
-                                // tile's reuse of the weight fragments wins: 415 vs 386 TFLOP/s
-        if (P == 1 && wgs(R, P) < 128)
-            R = 1;
-    }
+    conv_auto_tile(N, Cout, Ho, Wo, nchunk, stride, phases, onetap, tile_r, tile_p, g_conv_min_wgs, R, P);
 }
 
 static int conv_f16x3(const float *x, int N, int Cin, int H, int W, const void *wp, int Cout, const float *xamax,
@@ -1034,24 +985,9 @@ static int conv_f16x3(const float *x, int N, int Cin, int H, int W, const void *
                   "stride / in_up must be 1 or 2 (not both 2)");
     DCL_CHECK_ARG((size_t)8 * H * W + (size_t)H * W < ((size_t)1 << 31), "image plane too large");
     ConvArgs a;
-    a.x = x;
-    a.wp = (const uint4 *)wp;
-    a.y = y;
-    a.addend = addend;
-    a.bias = bias;
-    a.xamax = xamax;
-    a.wamax = wamax;
-    a.xcount = xcount;
-    a.N = N;
-    a.Cin = Cin;
-    a.Cout = Cout;
-    a.Hs = H;
-    a.Ws = W;
+    conv_fill_args(a, x, N, Cin, H, W, wp, Cout, xamax, xcount, wamax, addend, bias, y, pre_sc, pre_sh);
     a.up = in_up;
-    a.phases = 0;
     a.onetap = onetap;
-    a.pre_sc = pre_sc;
-    a.pre_sh = pre_sh;
     if (in_up == 2 && g_up2_phases) {
         // one parity class of the output per workgroup, over the stored input (see conv_body, PH)
         DCL_CHECK_ARG(Hout > 0 && Wout > 0 && (Hout - 1) / 2 + 1 == H && (Wout - 1) / 2 + 1 == W,

@@ -130,8 +130,17 @@ __device__ __forceinline__ void static_for(F &&f)
 // scale (gsc = 0), which multiplies the mapped value.  The staging items are dealt out so that an item's channel octet is
 // wave-uniform (waves 0-1: channels 0-7 of the chunk, waves 2-3: channels 8-15) and the eight (sc, sh) pairs of a chunk are
 // scalar registers: no vector register is spent on them (the (3, 4) tile has none to spare).
+//
+// LDS: two patch buffers, conv_lds_bytes() bytes aligned to 16, handed in by the caller -- the fused backward kernel
+// (dcl_convbwd.hip) shares one buffer between this body and the weight gradient's; the two-argument form below declares its own.
+template <int R, int P, int S, int WS = 1>
+constexpr int conv_lds_bytes()
+{
+    return 2 * ((S * (4 / WS * P - 1) + 3) * (S * (TW - 1) + 3)) * PIXB;     // 2 x rows x width of the patch (ROWS, LW below) x record
+}
+
 template <int R, int P, int S, int MODE = 0, bool IL = false, int WS = 1, bool PRE = false>
-__device__ __forceinline__ void conv_body(const ConvArgs &a, const int bid)
+__device__ __forceinline__ void conv_body(const ConvArgs &a, const int bid, unsigned char *lds)
 {
     constexpr bool PH = MODE == 1, T1 = MODE == 2;
     static_assert(!PRE || (IL && MODE == 0), "pre-activation: interleaved 3x3 tiles only");
@@ -144,7 +153,7 @@ __device__ __forceinline__ void conv_body(const ConvArgs &a, const int bid)
     constexpr int TP = ROWS * LW;
     constexpr int NITEM = PRE ? (TP + 127) / 128 : (2 * TP + 255) / 256;
     constexpr int BUFB = TP * PIXB;
-    __shared__ __attribute__((aligned(16))) unsigned char lds[2 * BUFB];
+    static_assert(2 * BUFB == conv_lds_bytes<R, P, S, WS>(), "LDS size");
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, h = lane >> 5, li = lane & 31;
     // channel octet (0 | 1) of staging item m of this thread: by position in the item sequence, or (PRE) by wave pair
@@ -674,6 +683,14 @@ __device__ __forceinline__ void conv_body(const ConvArgs &a, const int bid)
                 }
             }
         }
+}
+
+// the body on LDS of its own (every kernel of dcl_conv3x3.hip and dcl_conv3x3_pre.hip)
+template <int R, int P, int S, int MODE = 0, bool IL = false, int WS = 1, bool PRE = false>
+__device__ __forceinline__ void conv_body(const ConvArgs &a, const int bid)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char lds[conv_lds_bytes<R, P, S, WS>()];
+    conv_body<R, P, S, MODE, IL, WS, PRE>(a, bid, lds);
 }
 
 }  // namespace

@@ -39,8 +39,8 @@ struct WgradPlan {
 };
 
 // dcl_wgrad3x3d.hip: the stride-1 kernel with LDS-DMA operand staging; same grid, slabs and arguments as k_wgrad3x3
-bool dcl_wgrad_dma_supported(int nco, int nci);
-bool dcl_wgrad_dma_wave_mode_supported(int nco, int nci);
+inline bool dcl_wgrad_dma_supported(int nco, int nci) { return nco >= 1 && nco <= 3 && nci >= 1 && nci <= 2 && nco * nci <= 4; }
+inline bool dcl_wgrad_dma_wave_mode_supported(int nco, int nci) { return nco == 3 && nci == 1; }
 int dcl_wgrad_dma_launch(const WgradArgs &a, int nco, int nci, dim3 grid, hipStream_t s);
 // dcl_wgrad3x3_s2.hip: the output-pixel formulation of stride 2.  The plan fills tile, splits, grid, slabs and family; the launch
 // takes tensors, amax slots and the PRE map from `a` (kernel only: the caller sums the slabs).
@@ -92,20 +92,22 @@ __device__ __forceinline__ void wgrad_scales(const Args &a, float *wm, float &sx
     sg = pow2_scale(fmaxf(fmaxf(wm[4], wm[5]), fmaxf(wm[6], wm[7])));
 }
 
+// The decodes take the workgroup id `bid` from the caller (blockIdx.x; the fused backward kernel of dcl_convbwd.hip puts the
+// weight-gradient workgroups behind its data-gradient tiles and hands in the id counted from the first of them).
 // XCD-aware decode of the 1-D grid: consecutive workgroup ids go round-robin over the 8 XCDs, so
 // id = xcd + 8 * (pair + npairs * hi) puts every (co group, ci group) pair of one pixel split on the SAME XCD,
 // next to each other in dispatch order -- they stream the same dy / x rows, which then come out of that
 // XCD's L2 instead of being fetched once per pair.
 template <class Args>
-__device__ __forceinline__ void wgrad_decode_flat(const Args &a, int &pair, int &xsplit)
+__device__ __forceinline__ void wgrad_decode_flat(const Args &a, const unsigned bid, int &pair, int &xsplit)
 {
     const int nx8 = a.nx & ~7, main_blocks = nx8 * a.npairs;
-    if ((int)blockIdx.x < main_blocks) {
-        const int xcd = blockIdx.x & 7, rest = blockIdx.x >> 3;
+    if ((int)bid < main_blocks) {
+        const int xcd = bid & 7, rest = bid >> 3;
         pair = rest % a.npairs;
         xsplit = (rest / a.npairs) * 8 + xcd;
     } else {                                // the nx % 8 left-over pixel splits, in plain order
-        const int rest = blockIdx.x - main_blocks;
+        const int rest = bid - main_blocks;
         pair = rest % a.npairs;
         xsplit = nx8 + rest / a.npairs;
     }
@@ -117,9 +119,9 @@ __device__ __forceinline__ void wgrad_decode_flat(const Args &a, int &pair, int 
 // and rectangle q of XCD k takes the ids k + 8 * (32 q .. 32 q + 31): one XCD (32 CUs), adjacent dispatch
 // slots.  (Head convolution, 15 x 45 pairs: FETCH_SIZE 28.0 GiB -> 16.5 GiB per launch, 12.9 -> 12.5 ms.)
 // False: padding of the last rectangles (the whole workgroup leaves).
-__device__ __forceinline__ bool wgrad_decode_rect(const WgradArgs &a, int &pair, int &xsplit)
+__device__ __forceinline__ bool wgrad_decode_rect(const WgradArgs &a, const unsigned bid, int &pair, int &xsplit)
 {
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    const int xcd = bid & 7, slot = bid >> 3;
     const int unit = (slot >> 5) * 8 + xcd, idx = slot & 31;       // unit = (pixel split, rectangle)
     const int ncog = a.npairs / a.ncig, rects_i = (a.ncig + a.rect_i - 1) / a.rect_i;
     const int nrect = ((ncog + a.rect_c - 1) / a.rect_c) * rects_i;
@@ -134,11 +136,11 @@ __device__ __forceinline__ bool wgrad_decode_rect(const WgradArgs &a, int &pair,
 
 // Wave-dealt form (a.wave_mode, k_wgrad3x3d WAVE): XCD x owns a contiguous run of pairs, its 128 waves take (pair, split) jobs in
 // order -- wave_mode 2: pair fastest, 1: split fastest.  A wave without a job gets an empty run of pair 0 (wsplit = a.S).
-__device__ __forceinline__ void wgrad_decode_wave(const WgradArgs &a, int wave, int &pair, int &xsplit, int &wsplit)
+__device__ __forceinline__ void wgrad_decode_wave(const WgradArgs &a, const unsigned bid, int wave, int &pair, int &xsplit, int &wsplit)
 {
-    const int xcd = blockIdx.x & 7, base = a.npairs >> 3, rem = a.npairs & 7;
+    const int xcd = bid & 7, base = a.npairs >> 3, rem = a.npairs & 7;
     const int mine = base + (xcd < rem ? 1 : 0), first = xcd * base + min(xcd, rem);
-    const int job = (int)(blockIdx.x >> 3) * 4 + wave;
+    const int job = (int)(bid >> 3) * 4 + wave;
     const int pl = a.wave_mode == 2 ? job % mine : job / a.S, sp = a.wave_mode == 2 ? job / mine : job - pl * a.S;
     xsplit = 0;
     if (a.wave_mode == 2 ? sp < a.S : pl < mine) {

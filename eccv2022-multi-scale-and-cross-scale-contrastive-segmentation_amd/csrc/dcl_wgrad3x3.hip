@@ -20,6 +20,8 @@
 
 #include "dcl_common.h"
 #include "dcl_wgrad.h"
+#include "dcl_wgrad_plan.h"
+#include "dcl_wgrad_reduce.h"
 
 namespace {
 
@@ -37,10 +39,10 @@ __global__ __launch_bounds__(256, 1) void k_wgrad3x3(WgradArgs a)
     wgrad_scales(a, wm, sx, sg);
     int pair, xsplit;
     if (a.rect_mode) {
-        if (!wgrad_decode_rect(a, pair, xsplit))
+        if (!wgrad_decode_rect(a, blockIdx.x, pair, xsplit))
             return;
     } else
-        wgrad_decode_flat(a, pair, xsplit);
+        wgrad_decode_flat(a, blockIdx.x, pair, xsplit);
     const int split = xsplit * 4 + wave;           // a wave past the last split gets an empty run and adds zeros
     const int cog = pair / a.ncig, cig = pair - cog * a.ncig;
     const int co0 = cog * NCO * 16, ci0 = cig * NCI * 16;
@@ -256,178 +258,23 @@ __global__ __launch_bounds__(256, 1) void k_wgrad3x3(WgradArgs a)
     wgrad_reduce_store(acc, red, wave, lane, a.part, xsplit, a.Cout, a.Cin, co0, ci0, ci_ok, q4, j, sx, sg);
 }
 
-// dw[co][ci][tap] = sum_s part[s][tap][co][ci].  Block = 32 outputs x 8 slab groups: group g adds slabs g, g+8, ...
-// in order, the 8 partial sums are combined in order through LDS -> fixed summation tree, deterministic.
-template <int K>
-__global__ __launch_bounds__(256) void k_wgrad_reduce_t(const float *__restrict__ part, int S, int Cout, int Cin,
-                                                       float *__restrict__ dw)
-{
-    // K groups of 32 outputs per workgroup: 1 for the narrow layers (many slabs, few outputs: parallelism over the
-    // outputs matters), 4 for the wide ones (with one, the 1.3 M outputs of a 384-channel layer were 41 k workgroups of
-    // a few loads each -- 16 us, bound by the workgroup dispatch rate)
-    __shared__ float sh[K][8][32];
-    const int total = 9 * Cout * Cin;
-    const int lane = threadIdx.x & 31, g = threadIdx.x >> 5;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int idx = (blockIdx.x * K + k) * 32 + lane;       // (tap, co, ci) in slab order
-        float s0 = 0.f, s1 = 0.f;
-        if (idx < total) {
-            int q = g;
-            for (; q + 8 < S; q += 16) {
-                s0 += part[(size_t)q * total + idx];
-                s1 += part[(size_t)(q + 8) * total + idx];
-            }
-            if (q < S)
-                s0 += part[(size_t)q * total + idx];
-        }
-        sh[k][g][lane] = s0 + s1;
-    }
-    __syncthreads();
-    if (g < K) {
-        const int idx = (blockIdx.x * K + g) * 32 + lane;
-        if (idx < total) {
-            float s = sh[g][0][lane];
-#pragma unroll
-            for (int q = 1; q < 8; ++q)
-                s += sh[g][q][lane];
-            const int ci = idx % Cin;
-            const int co = (idx / Cin) % Cout;
-            const int tap = idx / (Cin * Cout);
-            dw[((size_t)co * Cin + ci) * 9 + tap] = s;
-        }
-    }
-}
-
-// Wide layers (few slabs, many outputs): one workgroup per (co, 32 ci), thread = (tap, ci).  The slab layout
-// [tap][co][ci] is read in 128-byte runs as before, but dw[co][ci][tap] is written through an LDS tile as ONE contiguous
-// 1152-byte run -- the per-output form writes 4 bytes every 36 (a 32-byte sector per value: 42 MB of write traffic for the
-// 5 MB gradient of a 384-channel layer).  Same slab order: bitwise the same sums when S <= 8 (one group per output).
-__global__ __launch_bounds__(320) void k_wgrad_reduce_wide(const float *__restrict__ part, int S, int Cout, int Cin,
-                                                          float *__restrict__ dw)
-{
-    __shared__ float tile[32 * 9];
-    const int co = blockIdx.y, ci0 = blockIdx.x * 32;
-    const int t = threadIdx.x, tap = t >> 5, cl = t & 31;
-    const size_t total = (size_t)9 * Cout * Cin;
-    if (t < 288) {
-        float s0 = 0.f;
-        if (ci0 + cl < Cin) {
-            const float *p = part + ((size_t)tap * Cout + co) * Cin + ci0 + cl;
-            for (int q = 0; q < S; ++q)
-                s0 += p[(size_t)q * total];
-        }
-        tile[cl * 9 + tap] = s0;
-    }
-    __syncthreads();
-    const int nci = min(32, Cin - ci0);
-    if (t < nci * 9)
-        dw[((size_t)co * Cin + ci0) * 9 + t] = tile[t];
-}
-
-static void launch_wgrad_reduce(const float *part, int S, int Cout, int Cin, float *dw, hipStream_t st)
-{
-    const int total = 9 * Cout * Cin;
-    if (total >= (1 << 18) && S <= 8)
-        hipLaunchKernelGGL(k_wgrad_reduce_wide, dim3((Cin + 31) / 32, Cout), dim3(320), 0, st, part, S, Cout, Cin, dw);
-    else if (total >= (1 << 18))
-        hipLaunchKernelGGL(k_wgrad_reduce_t<4>, dim3((total + 127) / 128), dim3(256), 0, st, part, S, Cout, Cin, dw);
-    else
-        hipLaunchKernelGGL(k_wgrad_reduce_t<1>, dim3((total + 31) / 32), dim3(256), 0, st, part, S, Cout, Cin, dw);
-}
-
 }  // namespace
 
-static int g_tile_nco = 0, g_tile_nci = 0;      // tuning override (dcl_wgrad3x3_set_tile), 0 = automatic
-static int g_force_nx = 0;                      // tuning override: pixel splits per tile pair (0 = automatic)
+static WgradTune g_tune;                        // tuning overrides (dcl_wgrad3x3_set_*): tile, splits, variant, wave form, strip groups
 static int g_wg_target = 256;                   // workgroups a launch aims at (pixel splits = target / tile pairs): one per CU;
                                                 // tuning hook dcl_wgrad3x3_set_workgroup_target for in-step A/B runs, where the
                                                 // launch shares the chip with the other branches' kernels
-static int g_variant = -1;     // 0 = MFMA-order operand loads (this file), -1 / 2 = LDS-DMA staging (dcl_wgrad3x3d.hip)
-
-// (A third variant -- workgroups handing the dY rows of a co group to each other through LDS, optional stream-K partition
-// -- reached the same kernel times as the LDS-DMA kernel with slabs four times the size and lost in the training step; it
-// was retired from the library in round 3: tools/probes/retired/dcl_wgrad3x3s.hip.)
-// per-wave kernel: operands staged by LDS-DMA (dcl_wgrad3x3d.hip) unless variant 0 asks for the direct loads; the direct
-// loads also serve tensors beyond the DMA kernel's 32-bit offsets and the zero-inserted stride-2 form
-static bool use_dma(int Cin, int H, int W) { return g_variant != 0 && (size_t)Cin * H * W * 4 < ((size_t)1 << 32); }
-
 static int g_s2_native = 1;     // stride 2: 1 = output-pixel formulation (dcl_wgrad3x3_s2.hip), 0 = zero-inserted dy
 
-static int g_wave_band = 0;     // wave form: rows per column of the traversal (0 = whole strips: the default -- 32-row bands
-                                // re-use the halo lines in L2 but pay a column prologue every 32 rows: 2.01 vs 1.91 ms on the head)
-static int g_strip_group = 1;   // waves of a workgroup on adjacent strips (WgradArgs::grp)
-static int g_wave_mode = 2;     // 129 .. 256 tile pairs of the (3, 1) tile: pixel splits dealt out to waves (dcl_wgrad3x3d.hip);
-                                // 2 = a workgroup's waves take the same split of four neighbouring pairs, 1 = four splits of a pair
-
-// The one launch plan: every decision between the shape and the launch is taken here, once.
+// The one launch plan: every decision between the shape and the launch is taken here, once (stride 1: dcl_wgrad_plan.h).
 static WgradPlan wgrad_plan(int N, int Cin, int Cout, int H, int W, int stride)
 {
-    WgradPlan p = {};
     if (stride == 2 && g_s2_native && dcl_wgrad_s2_supported(H, W)) {
-        dcl_wgrad_s2_plan(N, Cin, Cout, H, W, g_tile_nco, g_tile_nci, p);
+        WgradPlan p = {};
+        dcl_wgrad_s2_plan(N, Cin, Cout, H, W, g_tune.tile_nco, g_tune.tile_nci, p);
         return p;
     }
-    const int cot = Cout / 16, cit = Cin / 16;
-    // Tiles per wave, measured on the HRNet-W48 shapes at batch 12 (tools/wgrad_tiles.py, and bench.py with
-    // DCL_WGRAD_TILE: the step decides, the slabs of the larger tiles cost HBM traffic that the standalone timing does not
-    // show): three co tiles x one ci tile wherever the co tiles divide by three (48 ... 720 channels: step 122.3 ms
-    // against 122.8 with (2, 2) at 192 and (3, 2) at 384 channels); else the four-tile wave (2, 2), (2, 1), (1, 2), (1, 1).
-    if (cot % 3 == 0) {
-        p.nco = 3;
-        p.nci = 1;
-    } else {
-        p.nco = (cot % 2 == 0) ? 2 : 1;
-        p.nci = (cit % 2 == 0) ? 2 : 1;
-    }
-    if (g_tile_nco > 0 && cot % g_tile_nco == 0)
-        p.nco = g_tile_nco;
-    if (g_tile_nci > 0)
-        p.nci = g_tile_nci;
-    if (p.nco * p.nci > 4)      // a forced ci count beside three co tiles: no six-tile wave (as dcl_wgrad_s2_plan)
-        p.nci = 1;
-    const bool dma = stride == 1 && use_dma(Cin > Cout ? Cin : Cout, H, W);
-    p.family = dma && dcl_wgrad_dma_supported(p.nco, p.nci) ? WGRAD_DMA : WGRAD_DIRECT;
-    p.ncig = (cit + p.nci - 1) / p.nci;
-    p.npairs = (cot / p.nco) * p.ncig;
-    p.units = N * ((W + 31) / 32);          // columns: (image, 32-pixel strip), H input rows each
-    // One workgroup (4 waves = 4 splits of one pair) per CU is all that fits (a wave owns most of its SIMD's
-    // registers): at most 256 workgroups, or the stragglers run as a second round and double the kernel time.
-    int nx = g_wg_target / p.npairs;
-    if (g_force_nx > 0)
-        nx = g_force_nx;
-    if (nx < 1)
-        nx = 1;         // more tile pairs than CUs (head convolution): one pixel split; finer splits were tried and
-                        // lose (3 splits fill the last round better but take 26 ms against 12.5 ms)
-    p.S = 4 * nx;
-    if ((long long)p.S > (long long)p.units * H)
-        p.S = p.units * H;
-    // one workgroup per pair and CUs left over: the splits go to single waves, S = 128 / (pairs of one XCD) of them
-    const int sw = 128 / ((p.npairs + 7) / 8);
-    const bool wm = dma && g_wave_mode && g_force_nx == 0 && p.npairs > 128 && p.npairs <= 256 && sw > 4 &&
-                    dcl_wgrad_dma_wave_mode_supported(p.nco, p.nci) && (long long)sw <= (long long)p.units * H;
-    if (wm)
-        p.S = sw;
-    p.wave_mode = wm ? g_wave_mode : 0;
-    p.band = (wm && g_wave_band > 0 && H % g_wave_band == 0 && H > g_wave_band) ? g_wave_band : H;
-    p.nx = (p.S + 3) / 4;                                    // workgroups per pair (4 splits each)
-    // adjacent strips for the waves of a workgroup (dcl_wgrad3x3d.hip): unclamped split count, strips in fours / pairs
-    p.grp = 1;
-    if (g_strip_group && !wm && p.S == 4 * p.nx && p.S >= 4) {
-        const int strips = (W + 31) / 32;
-        p.grp = (strips % 4 == 0) ? 4 : ((strips % 2 == 0) ? 2 : 1);
-    }
-    p.grid = (unsigned)(p.npairs * p.nx);        // exactly the populated workgroups, <= 256 whenever pairs <= 256
-    p.rect_i = p.ncig >= 16 ? 16 : (p.ncig >= 8 ? 8 : (p.ncig >= 4 ? 4 : (p.ncig >= 2 ? 2 : 1)));
-    p.rect_c = 32 / p.rect_i;
-    p.rect_mode = p.npairs > 128 ? 1 : 0;
-    if (p.rect_mode) {
-        const int ncog = p.npairs / p.ncig;
-        const int units_r = ((ncog + p.rect_c - 1) / p.rect_c) * ((p.ncig + p.rect_i - 1) / p.rect_i) * p.nx;
-        p.grid = (unsigned)(((units_r + 7) / 8) * 8 * 32);
-    }
-    p.slabs = wm ? p.S : p.nx;                  // one slab per wave-level split, or per workgroup (4 splits)
-    return p;
+    return wgrad_plan_stride1(N, Cin, Cout, H, W, stride, g_tune, g_wg_target, 128);
 }
 
 extern "C" int dcl_wgrad3x3_set_tile(int nco, int nci)
@@ -435,8 +282,8 @@ extern "C" int dcl_wgrad3x3_set_tile(int nco, int nci)
     // only tiles with an instantiated kernel (the six-tile wave (3, 2) spilled: retired)
     if (nco < 0 || nco > 3 || nci < 0 || nci > 2 || (nco == 3 && nci == 2))
         return DCL_EINVAL;
-    g_tile_nco = nco;
-    g_tile_nci = nci;
+    g_tune.tile_nco = nco;
+    g_tune.tile_nci = nci;
     return 0;
 }
 
@@ -444,7 +291,7 @@ extern "C" int dcl_wgrad3x3_set_variant(int variant)
 {
     if (variant < -1 || variant > 2 || variant == 1)     // 1 was the retired kernel
         return DCL_EINVAL;
-    g_variant = variant;
+    g_tune.variant = variant;
     dcl_wgrad_s2_set_dma(variant != 0);      // the stride-2 kernel's LDS-DMA form follows the same switch
     return 0;
 }
@@ -457,25 +304,25 @@ extern "C" int dcl_wgrad3x3_set_workgroup_target(int n)
 
 extern "C" int dcl_wgrad3x3_set_splits(int nx)
 {
-    g_force_nx = nx > 0 ? nx : 0;
+    g_tune.force_nx = nx > 0 ? nx : 0;
     return 0;
 }
 
 extern "C" int dcl_wgrad3x3_set_wave_mode(int on)
 {
-    g_wave_mode = on < 0 ? 0 : on;
+    g_tune.wave_mode = on < 0 ? 0 : on;
     return 0;
 }
 
 extern "C" int dcl_wgrad3x3_set_wave_band(int rows)
 {
-    g_wave_band = rows > 0 ? rows : 0;
+    g_tune.wave_band = rows > 0 ? rows : 0;
     return 0;
 }
 
 extern "C" int dcl_wgrad3x3_set_strip_group(int on)
 {
-    g_strip_group = on ? 1 : 0;
+    g_tune.strip_group = on ? 1 : 0;
     return 0;
 }
 
@@ -543,35 +390,7 @@ static int wgrad3x3_impl(const float *x, const float *dy, int N, int Cin, int Co
     DCL_CHECK_ARG(((((uintptr_t)x) | ((uintptr_t)dy)) & 15) == 0, "tensors must be 16-byte aligned");
     const WgradPlan p = wgrad_plan(N, Cin, Cout, H, W, stride);
     WgradArgs a;
-    a.x = x;
-    a.dy = dy;
-    a.part = part;
-    a.xamax = xamax;
-    a.gamax = gamax;
-    a.xcount = xcount;
-    a.gcount = gcount;
-    a.N = N;
-    a.Cin = Cin;
-    a.Cout = Cout;
-    a.H = H;
-    a.W = W;
-    a.Hd = stride == 2 ? (H - 1) / 2 + 1 : H;
-    a.Wd = stride == 2 ? W / 2 : W;
-    a.strips = (W + 31) / 32;
-    a.nseg = 1;
-    a.pre_sc = pre_sc;
-    a.pre_sh = pre_sh;
-    a.units = p.units;
-    a.S = p.S;
-    a.ncig = p.ncig;
-    a.npairs = p.npairs;
-    a.nx = p.nx;
-    a.rect_c = p.rect_c;
-    a.rect_i = p.rect_i;
-    a.rect_mode = p.rect_mode;
-    a.wave_mode = p.wave_mode;
-    a.band = p.band;
-    a.grp = p.grp;
+    wgrad_fill_args(a, p, x, dy, part, xamax, xcount, gamax, gcount, N, Cin, Cout, H, W, stride, pre_sc, pre_sh);
     const dim3 grid(p.grid);
     hipStream_t s = (hipStream_t)stream;
     if (p.family == WGRAD_S2 || p.family == WGRAD_S2_DMA) {

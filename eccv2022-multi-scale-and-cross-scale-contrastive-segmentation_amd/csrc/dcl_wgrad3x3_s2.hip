@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256, 1) void k_wgrad3x3_s2(WgradS2Args a)
     float sx, sg;
     wgrad_scales(a, wm, sx, sg);
     int pair, xsplit;
-    wgrad_decode_flat(a, pair, xsplit);         // the tile pairs of one pixel split share an XCD (and its L2)
+    wgrad_decode_flat(a, blockIdx.x, pair, xsplit);         // the tile pairs of one pixel split share an XCD (and its L2)
     const int split = xsplit * 4 + wave;           // a wave past the last split gets an empty run and adds zeros
     const int cog = pair / a.ncig, cig = pair - cog * a.ncig;
     const int co0 = cog * NCO * 16, ci0 = cig * NCI * 16;
@@ -247,7 +247,7 @@ __global__ __launch_bounds__(256, 1) void k_wgrad3x3_s2d(WgradS2Args a)
     float sx, sg;
     wgrad_scales(a, wm, sx, sg);
     int pair, xsplit;
-    wgrad_decode_flat(a, pair, xsplit);         // the tile pairs of one pixel split share an XCD (and its L2)
+    wgrad_decode_flat(a, blockIdx.x, pair, xsplit);         // the tile pairs of one pixel split share an XCD (and its L2)
     const int split = xsplit * 4 + wave;
     const int cog = pair / a.ncig, cig = pair - cog * a.ncig;
     const int co0 = cog * NCO * 16, ci0 = cig * NCI * 16;

@@ -27,6 +27,9 @@ class DebugConfig:
     # classifier's weights (models/ops_head.py _HeadNormClassifier); 0 = the norm writes its 720-channel output (A/B runs)
     fuse_bn_apply: bool = field(default_factory=lambda: _flag('DCL_FUSE_BN_APPLY'))             # bn1 + ReLU of a residual block inside
     # conv2's operand staging (models/fused_bn.py PreAct, csrc/dcl_conv3x3_pre.hip); 0 = the norm writes its output (A/B runs)
+    fuse_conv_bwd: bool = field(default_factory=lambda: _flag('DCL_FUSE_CONV_BWD', False))      # 1 = data + weight gradient of the 192-
+    # and 384-channel 3x3 convolutions in one launch (models/ops_conv.py, csrc/dcl_convbwd.hip).  Ships OFF: 40 us faster per launch
+    # stand-alone, no gain in the multi-stream step (profiles/convbwd_ab.txt)
     branch_streams: bool = field(default_factory=lambda: _flag('DCL_BRANCH_STREAMS'))           # one HIP stream per branch
     defer_join: bool = field(default_factory=lambda: _flag('DCL_DEFER_JOIN'))                   # no join between modules
     stage_continuity: bool = field(default_factory=lambda: _flag('DCL_STAGE_CONTINUITY'))       # ... nor between stages

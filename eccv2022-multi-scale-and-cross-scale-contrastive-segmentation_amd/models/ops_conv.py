@@ -203,6 +203,40 @@ def conv3x3_wgrad_pre(x, gy, pre_sc, pre_sh, pre_amax, stride=1):
     return dw
 
 
+FUSE_CONV_BWD = _dbg.fuse_conv_bwd       # DCL_FUSE_CONV_BWD=1: data + weight gradient in one launch (default: two launches -- the fused
+                                         # launch wins 40 us alone and nothing in the multi-stream step)
+
+
+def conv3x3_bwd_fused_applies(x, cout, pre=False):
+    """Whether the backward of a 3x3 / stride 1 convolution of x with ``cout`` output channels runs as one launch
+    (csrc/dcl_convbwd.hip): the switch is on, the library is built and its automatic plan takes the shape -- the 192- and 384-channel
+    BasicBlock shapes, whose data-gradient tiles fill less than half the chip."""
+    if not FUSE_CONV_BWD:
+        return False
+    from .. import _lib_convbwd as cb
+    n, ci, h, w = x.shape
+    return cb.built() and x.dtype == torch.float32 and x.is_contiguous() and cb.supported(n, ci, cout, h, w, pre)
+
+
+def conv3x3_bwd_fused(x, gy, wpt, wamax, addend=None, pre=None, tile=(0, 0), wg_target=0):
+    """(gx, dw) of conv2d(x, w, padding=1) for the output gradient gy in one launch; wpt: w packed for the data gradient, ``addend``
+    is added to gx, ``pre`` = (sc, sh, amax): x is the RAW tensor in front of a norm and the operand relu(x * sc + sh)."""
+    from .. import _lib_convbwd as cb
+    from .amax import amax_of
+    n, ci, h, w = x.shape
+    co = gy.shape[1]
+    L = cb.lib()
+    part, dw = _wgrad_buffers("conv3x3_bwd_fused", L.dcb_wgrad_splits(n, ci, co, h, w, tile[0], tile[1], wg_target), co, ci, 3, x.device)
+    gx = torch.empty_like(x)
+    ga = amax_of(gy)
+    sc, sh, xa = pre if pre is not None else (None, None, amax_of(x))
+    cb.check(L.dcb_conv3x3_bwd_f16x3(cb.ptr(gy), cb.ptr(wpt), cb.ptr(x), n, ci, co, h, w, cb.ptr(ga), ga.numel(), cb.ptr(wamax),
+                                     cb.ptr(xa), xa.numel(), cb.ptr(addend), cb.ptr(sc), cb.ptr(sh), tile[0], tile[1], wg_target,
+                                     cb.ptr(gx), cb.ptr(part), cb.ptr(dw), _stream(x)), "dcb_conv3x3_bwd_f16x3")
+    cb.calls["bwd"] += 1
+    return gx, dw
+
+
 def stem_wgrad_supported(x, cout, stride):
     return stride == 2 and x.shape[1] * 9 <= 32 and cout <= 64 and x.is_contiguous() and x.dtype == torch.float32
 
@@ -289,6 +323,17 @@ class _Conv3x3Direct(torch.autograd.Function):
             x, weight = ctx.saved_tensors
         gy = gy.contiguous()
         gx = gw = None
+        if ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and not ctx.k1 and ctx.stride == 1 \
+                and conv3x3_bwd_fused_applies(x, weight.shape[0], ctx.pre):
+            # both gradients in one launch: the weight gradient on the compute units the data-gradient tiles leave free
+            addend = None
+            if ctx.token is not None and ctx.token.dres is not None:
+                addend, ctx.token.dres = ctx.token.dres, None            # gradient of the residual branch, fused in
+            wamax, _, wpt = ctx.mod.packed_weights()
+            pre = (pre_sc, pre_sh, pre_amax) if ctx.pre else None
+            gx, gw = conv3x3_bwd_fused(x, gy, wpt, wamax, addend, pre)
+            gb = gy.sum((0, 2, 3)) if (ctx.has_bias and ctx.needs_input_grad[4]) else None
+            return gx, gw, None, None, gb
         if ctx.needs_input_grad[0]:
             wamax, _, wpt = ctx.mod.packed_weights()
             gx = torch.empty_like(x)

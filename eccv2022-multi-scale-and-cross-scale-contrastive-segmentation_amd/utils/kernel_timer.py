@@ -164,8 +164,24 @@ def _wgrad3x3_pre(a):
         f"{n}x({ci}->{co})x{h}x{w}" + (" s2" if stride == 2 else "") + " pre"
 
 
-# entry point -> (work model, bound, fixed kernel symbol or None = ask dcl_last_kernel)
+def _conv3x3_bwd(a):
+    # (gy, wpt, x, N, Cin, Cout, H, W, gamax, gcount, wamax, xamax, xcount, addend, pre_sc, pre_sh, tile_r, tile_p, wg_target, gx, part,
+    # dw, stream): data gradient + weight gradient of one convolution in one launch (libdcl_convbwd.so) -- the work of both
+    n, ci, co, h, w = a[3], a[4], a[5], a[6], a[7]
+    return 2.0 * 2.0 * n * co * ci * 9 * h * w, 4.0 * n * (2 * ci + 2 * co) * h * w + (4.0 * n * ci * h * w if a[13] else 0.0), \
+        f"{n}x({ci}->{co})x{h}x{w}" + (" pre" if a[14] else "")
+
+
+def _conv3x3_bwd_symbol(a):
+    # the instantiation the entry launches: k_conv3x3_bwd<P, WAVE, PRE> (csrc/dcl_convbwd.hip), from the plan it uses
+    from .. import _lib_convbwd
+    p = _lib_convbwd.plan(a[3], a[4], a[5], a[6], a[7], a[16], a[17], a[18])
+    return f"k_conv3x3_bwd<{p['tile_p']},{'true' if p['wave_mode'] else 'false'},{'true' if a[14] else 'false'}>"
+
+
+# entry point -> (work model, bound, fixed kernel symbol or None = ask dcl_last_kernel); dcb_*: entries of libdcl_convbwd.so
 MODELS = {
+    "dcb_conv3x3_bwd_f16x3": (_conv3x3_bwd, "mfma", "k_conv3x3_bwd"),
     "dcl_conv3x3_f16x3": (_conv3x3, "mfma", None),
     "dcl_conv3x3_s2_smallcin": (_conv_smallcin, "hbm", "k_conv3x3_s2_smallcin"),
     "dcl_wgrad3x3_s2_smallcin": (_wgrad_smallcin, "hbm", "k_wgrad_stem"),
@@ -208,10 +224,21 @@ class KernelTimer:
         L = _lib.lib()
         L.dcl_trace_kernels(1)
         for name in self.names:
-            fn = getattr(L, name)
+            lib_of = self._library(name)
+            if lib_of is None:
+                continue
+            fn = getattr(lib_of, name)
             self._orig[name] = fn
-            setattr(L, name, self._wrap(L, name, fn))
+            setattr(lib_of, name, self._wrap(L, name, fn))
         return self
+
+    @staticmethod
+    def _library(name):
+        """the loaded library that holds the entry (None: a satellite that is not built)"""
+        if name.startswith("dcb_"):
+            from .. import _lib_convbwd
+            return _lib_convbwd.lib() if _lib_convbwd.built() else None
+        return _lib.lib()
 
     def _wrap(self, L, name, fn):
         model, _, fixed = MODELS[name]
@@ -224,7 +251,9 @@ class KernelTimer:
             e1.record()
             sym = fixed or (L.dcl_last_kernel() or b"?").decode()
             flops, byts, shape = model(a)
-            if name == "dcl_bn_apply_fused":
+            if name == "dcb_conv3x3_bwd_f16x3":
+                sym = _conv3x3_bwd_symbol(a)
+            elif name == "dcl_bn_apply_fused":
                 sym = f"k_bn_apply<{'true' if a[11] else 'false'},{'true' if a[1] else 'false'}>"
             elif name == "dcl_bn_apply_parts":
                 sym = f"k_bn_apply<{'true' if a[12] else 'false'},{'true' if a[1] else 'false'}>"
@@ -237,7 +266,7 @@ class KernelTimer:
     def __exit__(self, *exc):
         L = _lib.lib()
         for name, fn in self._orig.items():
-            setattr(L, name, fn)
+            setattr(self._library(name), name, fn)
         L.dcl_trace_kernels(0)
         return False
 
