@@ -41,7 +41,7 @@ __device__ __forceinline__ size_t wide_plane(const Slice &s, size_t p) { return 
 __global__ __launch_bounds__(256) void k_upsample_fwd(const float *__restrict__ x,
                                                      const float *__restrict__ addend, int h, int w,
                                                      int H, int W, Axis ay, Axis ax, int relu, float *__restrict__ y,
-                                                     Slice sl, int tpr, int nrows)
+                                                     Slice sl, int tpr, int nrows, int vec)
 {
     const int row = blockIdx.x * (256 / tpr) + threadIdx.x / tpr;              // (n*C + c) * H + oy
     if (row >= nrows)
@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void k_upsample_fwd(const float *__restrict__ 
     const float *r1 = x + (plane * h + y1) * (size_t)w;
     float *out = y + (wide_plane(sl, plane) * H + oy) * (size_t)W;
     const float *add = addend ? addend + (size_t)row * W : nullptr;     // y = addend + upsample(x)
-    const bool vec = (W & 3) == 0;
+    // vec (host): W % 4 == 0 and y, addend 16-byte aligned -- then every row of either starts on a 16-byte boundary
     for (int ox4 = tx * 4; ox4 < W; ox4 += tpr * 4) {
         float v[4];
 #pragma unroll
@@ -199,9 +199,12 @@ static int upsample_fwd(const float *x, const float *addend, int planes, int h, 
     while (tpr < 256 && tpr * 4 < W)
         tpr *= 2;
     const int nrows = planes * H, rpb = 256 / tpr;
+    // the 16-byte loads of the addend and stores of y need both on a 16-byte boundary (a contiguous view at an odd storage
+    // offset is not); the scalar path otherwise
+    const int vec = (W & 3) == 0 && ((((uintptr_t)y) | ((uintptr_t)addend)) & 15) == 0;
     hipLaunchKernelGGL(k_upsample_fwd, dim3((unsigned)((nrows + rpb - 1) / rpb)), dim3(256), 0, (hipStream_t)stream, x,
                        addend, h, w, H, W, make_axis(h, H, align_corners), make_axis(w, W, align_corners), relu, y, sl, tpr,
-                       nrows);
+                       nrows, vec);
     DCL_LAUNCH_CHECK();
     return 0;
 }

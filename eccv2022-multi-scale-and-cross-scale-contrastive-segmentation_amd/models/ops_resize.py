@@ -112,6 +112,14 @@ class _FanOut(torch.autograd.Function):
         while len(gs) > 1:
             part, gs = gs[:4], gs[4:]
             out = torch.empty_like(part[0])
+            if any(t.data_ptr() & 15 for t in part + [out]):
+                # dcl_add_n reads and writes 16 B per lane; a contiguous gradient at an odd storage offset (the dim-0 narrow
+                # that torch.cat's backward hands out) is summed by plain adds in the same left-to-right order: same bits
+                torch.add(part[0], part[1], out=out)
+                for t in part[2:]:
+                    out.add_(t)
+                gs = [out] + gs
+                continue
             p = [_lib.ptr(t) for t in part] + [None] * (4 - len(part))
             _lib.check(L.dcl_add_n(p[0], p[1], p[2], p[3], out.numel(), _lib.ptr(out), _lib.stream_ptr(out.device)),
                        "dcl_add_n")
